@@ -17,7 +17,17 @@ resident in HBM (pre-tokenize + routing, BPE merge passes, id emission + token o
 with the host reading the token count).  `value` = bytes of all shards x steps / max-over-ranks
 wall time of the K timed steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2] [--cpu-seconds S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2] [--dump-outputs DIR] [--full [--cpu-seconds S]]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step`, and the per-kernel figures the timed steps' own HIP events give).  --full adds what
+takes work of its own, after the timed steps or outside them: the parity vote against the golden
+digests, the user-facing e2e / python rates, the CPU baseline and the PMC traffic record
+(--no-parity / --no-user-facing / --no-cpu-baseline drop single parts of it).
+
+--dump-outputs DIR writes what the last timed step left in the caller's buffers as DIR/<name>.npy
+(dump_outputs below): the token count, and fixed seeded samples of the ids and of the token
+offsets.  The inputs are seeded, so two builds run with the same arguments compare file for file.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, N child processes (one per GPU) are
 started before anything touches the GPU; under torch.distributed.run the ranks come from
@@ -162,6 +172,35 @@ def user_facing(tok, text, off, ids_dev, toff_dev, reps, py_docs):
     }
 
 
+DUMP_IDS, DUMP_OFFS = 4_000_000, 2_000_000  # elements kept per array: 16 MB of f32 + 16 MB of f64
+
+
+def dump_outputs(outdir, rank, d_ids, d_tok_off, ntok):
+    """What the last timed step returned to its caller, as .npy files under `outdir` (rank r > 0
+    appends `_rank<r>` to the names):
+      n_tokens         f64[1]  the call's return value (ids written)
+      ids_sample       f32[<= DUMP_IDS]   ids[j] at sorted positions j drawn from [0, n_tokens) by a
+                               fixed seed (every id when there are no more than DUMP_IDS; ids < 2^24
+                               are exact in f32)
+      tok_off_sample   f64[<= DUMP_OFFS]  tok_off[d] at sorted doc indices d drawn from [0, D] by the
+                               same generator (every offset when there are no more than DUMP_OFFS)
+    The samples are gathered on the device, so only they cross to the host."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng([0x44554D50, rank])
+
+    def sample(t, keep, dtype):
+        if len(t) > keep:
+            t = t[torch.from_numpy(np.sort(rng.integers(0, len(t), size=keep))).to(t.device)]
+        return t.cpu().numpy().astype(dtype)
+
+    arrays = {"n_tokens": np.array([ntok], dtype=np.float64),
+              "ids_sample": sample(d_ids[:ntok], DUMP_IDS, np.float32),
+              "tok_off_sample": sample(d_tok_off, DUMP_OFFS, np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, "%s%s.npy" % (name, "" if rank == 0 else "_rank%d" % rank)), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -208,7 +247,7 @@ def workload(args, rank, world):
         text, off = z["text"], z["off"]
     else:
         text, off = corpus.corpus_c4_range(d0, d1, n, workers=1 if (args.corpus_workers == 1 or profiled) else
-                                           max(1, min(8, cpus // world)))
+                                           max(1, min(16, cpus // world)))
         try:
             os.makedirs(os.path.dirname(cache), exist_ok=True)
             np.savez(cache + ".tmp.npz", text=text, off=off)
@@ -228,13 +267,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=["c4", "c2"], default="c4")
     ap.add_argument("--docs", type=int, default=0, help="override the doc count (tests; parity needs the default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (token count, seeded samples of ids and token "
+                         "offsets) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity vote, the user-facing rates, the CPU baseline "
+                         "and the PMC traffic lookup (a plain run does none of them)")
     ap.add_argument("--cpu-seconds", type=float, default=16.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: no parity vote")
     ap.add_argument("--corpus-workers", type=int, default=0, help="1: build the corpus without a process pool")
-    ap.add_argument("--no-user-facing", action="store_true", help="skip the e2e / python rates (rank 0, after timing)")
+    ap.add_argument("--no-user-facing", action="store_true", help="with --full: skip the e2e / python rates (rank 0, after timing)")
     ap.add_argument("--py-docs", type=int, default=100_000)
     args = ap.parse_args()
+    if not args.full:
+        args.no_parity = args.no_cpu_baseline = args.no_user_facing = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -367,6 +414,9 @@ def main():
     b_alg = B + 4 * T + 16 * (D + 1)
     ms_dev = avg("ms_device")
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, d_ids, d_tok_off, ntok)
+
     uf = None
     if rank == 0 and not args.no_user_facing:
         ids_dev = d_ids[:ntok].cpu().numpy().view(np.uint32)
@@ -383,9 +433,9 @@ def main():
             cpu = cpu_baseline(tok_path, text, off, args.cpu_seconds)
         # HBM bytes per launch of the dominant kernel from the committed PMC passes -- only when
         # they profiled this very library build (sha256 of the loaded libctok.so) and workload
-        traffic, traffic_src = None, "no PMC record for this workload"
+        traffic, traffic_src = None, "no PMC record for this workload" if args.full else "not looked up without --full"
         tr_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tr_path):
+        if args.full and os.path.exists(tr_path):
             from complexity_tokenizer import _native
             with open(_native.LIB_PATH, "rb") as fh:
                 lib_sha = hashlib.sha256(fh.read()).hexdigest()

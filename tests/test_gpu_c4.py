@@ -124,7 +124,7 @@ def _bench_ranks(c4, world, extra=()):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     proc = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2",
-                           "--warmup", "1", "--no-cpu-baseline"] + list(extra), cwd=ROOT, env=env, capture_output=True,
+                           "--warmup", "1", "--full", "--no-cpu-baseline"] + list(extra), cwd=ROOT, env=env, capture_output=True,
                           text=True, timeout=540)
     sys.stderr.write(proc.stderr[-4000:])
     assert proc.returncode == 0, proc.stderr[-4000:]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU-box session (run through gpurun from the repo root).  Steps, chained so that the first
 # failure ends the session, each under its own time limit:
-#   tests   pytest -m gpu (whole suite)          bench   bench.py default line (C4, CPU baseline)
+#   tests   pytest -m gpu (whole suite)          bench   bench.py --full line (C4, CPU baseline)
 #   prof    rocprofv3 kernel trace of bench.py   pmc     FETCH_SIZE / WRITE_SIZE passes -> traffic
 #   pmccopy the session's traffic record to profiles/pmc_traffic.json (bench.py reads it)
 #   ab:CFG:FIX:LIB_A:LIB_B   alternating kernel-only probes (tools/probe.py) of two libraries
@@ -40,7 +40,7 @@ for step in "$@"; do
       grep -E "^(FAILED|ERROR)" "$OUT/ptest.log" || true
       if [ -n "$STRICT" ] && [ $rc -ne 0 ]; then echo "ptest: failures (STRICT): session ends"; exit 1; fi ;;
     bench)
-      timeout -k 10 500 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.log" || { tail -20 "$OUT/bench.log"; exit 1; }
+      timeout -k 10 500 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.log" || { tail -20 "$OUT/bench.log"; exit 1; }
       cat "$OUT/bench.json" ;;
     prof)
       (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
