@@ -123,6 +123,12 @@ class TrainerConfig(ctypes.Structure):  # include/ctok_trainer.h
                 ("n_special", ctypes.c_uint64), ("device", ctypes.c_int)]
 
 
+class TrainerCountStats(ctypes.Structure):  # include/ctok_trainer.h ctok_trainer_count_info
+    _fields_ = [("pieces", ctypes.c_uint64), ("words", ctypes.c_uint64), ("unique_words", ctypes.c_uint64),
+                ("chunks", ctypes.c_uint64), ("host_chunks", ctypes.c_uint64), ("rerun_chunks", ctypes.c_uint64),
+                ("bytes_d2h", ctypes.c_uint64), ("ms_device", ctypes.c_double), ("ms_host", ctypes.c_double)]
+
+
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -175,6 +181,8 @@ SIGS = {
     "ctok_trainer_initial_pairs": (ctypes.c_int, [_p, _p, _p, _p, _u64, _u64p]),
     "ctok_trainer_timing": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                            ctypes.POINTER(ctypes.c_double)]),
+    "ctok_trainer_word_counts": (ctypes.c_int, [_p, ctypes.c_int, _p, _u64, _p, _p, _u64, _u64p, _u64p]),
+    "ctok_trainer_count_stats": (ctypes.c_int, [_p, ctypes.POINTER(TrainerCountStats)]),
 }
 
 for _name, (_res, _args) in SIGS.items():

@@ -1,7 +1,8 @@
 """`complexity_tokenizer.Trainer`: the INL-BPE trainer (reference src/bindings/trainers.rs:10-92 over
 src/trainer.rs) with its pair counting on the GPU, through include/ctok_trainer.h.
 
-Word counting pre-tokenizes on the GPU (NFC + ByteLevel, the encode path's k_segment); the pair
+Word counting pre-tokenizes on the GPU (NFC + ByteLevel, the encode path's k_segment) and counts the
+words there in a device hash table (csrc/wordcount.hip; CTOK_TRAIN_COUNT=host: on host threads); the pair
 histogram and each merge's pass over the words run on the GPU; the INL-scored heap runs in the
 native host runtime.  There is no CPU fallback: without a HIP device the calls raise DeviceError.
 """
@@ -153,6 +154,35 @@ class Trainer:
         rc = _n.lib.ctok_trainer_train_words(self._h, blob.ctypes.data, off.ctypes.data, freqs.ctypes.data, len(words))
         if rc:
             _raise(rc)
+
+    def word_counts(self, accumulator=True):
+        """The current word counts as a {raw-bytes word: count} dict (the keys train_from_word_freqs
+        accepts): the accumulator of count_batch, or with accumulator=False the counts of a
+        train(files) / train_from_iterator in progress; extension, the reference keeps them private."""
+        acc = 1 if accumulator else 0
+        nw, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = _n.lib.ctok_trainer_word_counts(self._h, acc, None, 0, None, None, 0, ctypes.byref(nw), ctypes.byref(nb))
+        if rc:
+            _raise(rc)
+        blob = np.zeros(nb.value + 1, dtype=np.uint8)
+        off = np.zeros(nw.value + 1, dtype=np.uint64)
+        freqs = np.zeros(nw.value + 1, dtype=np.uint32)
+        rc = _n.lib.ctok_trainer_word_counts(self._h, acc, blob.ctypes.data, nb.value, off.ctypes.data, freqs.ctypes.data,
+                                             nw.value, ctypes.byref(nw), ctypes.byref(nb))
+        if rc:
+            _raise(rc)
+        raw, o, f = blob.tobytes(), off.tolist(), freqs.tolist()
+        return {raw[o[i]:o[i + 1]]: f[i] for i in range(nw.value)}
+
+    def count_stats(self) -> dict:
+        """What the last counting call (count_batch, or the last block of train / train_from_iterator)
+        did: pieces, words, unique_words, chunks, host_chunks, rerun_chunks, bytes_d2h, ms_device,
+        ms_host (include/ctok_trainer.h); extension."""
+        st = _n.TrainerCountStats()
+        rc = _n.lib.ctok_trainer_count_stats(self._h, ctypes.byref(st))
+        if rc:
+            _raise(rc)
+        return {name: getattr(st, name) for name, _ in st._fields_}
 
     def to_str(self) -> str:
         """The tokenizer.json `save` writes (src/trainer.rs:600-645)."""

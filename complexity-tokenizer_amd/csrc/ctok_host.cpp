@@ -35,6 +35,7 @@
 #include "ctok_internal.h"
 #include "gen/regex_props.h"
 #include "gen/unicode_data.h"
+#include "host_common.h"
 #include "json.hpp"
 
 using namespace ctok_dev;
@@ -2496,7 +2497,8 @@ unsigned usable_cpus() { return usable_cpus_once(); }
 // dev: the text the pieces index (normalised when normalisation ran), its doc offsets, and the
 // piece-start bitmap (bit g = a piece starts at byte g).
 void pretokenize(ctok* t, int dev, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs,
-                 std::vector<uint8_t>& text, std::vector<uint64_t>& off, std::vector<uint32_t>& pbits) {
+                 std::vector<uint8_t>& text, std::vector<uint64_t>& off, std::vector<uint32_t>& pbits,
+                 uint64_t* bytes_d2h) {
   if (doc_off[0] != 0) throw_err(CTOK_E_ARG, "offsets[0] must be 0");
   for (uint64_t d = 0; d < n_docs; d++)
     if (doc_off[d + 1] < doc_off[d]) throw_err(CTOK_E_ARG, "offsets must be non-decreasing");
@@ -2527,6 +2529,37 @@ void pretokenize(ctok* t, int dev, const uint8_t* utf8, const uint64_t* doc_off,
     if (B) std::memcpy(text.data(), utf8, B);
     std::memcpy(off.data(), doc_off, (n_docs + 1) * 8);
   }
+  if (bytes_d2h) *bytes_d2h = pbits.size() * 4 + (ds->last_norm ? B + (n_docs + 1) * 8 : 0);
+}
+
+// The same pre-tokenization with nothing copied back: `use` runs under the device's mutex with the
+// device-resident text, doc offsets and piece-start bitmap, which stay valid until it returns.
+void pretokenize_device(ctok* t, int dev, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs,
+                        const std::function<void(const DevicePretok&)>& use) {
+  if (doc_off[0] != 0) throw_err(CTOK_E_ARG, "offsets[0] must be 0");
+  for (uint64_t d = 0; d < n_docs; d++)
+    if (doc_off[d + 1] < doc_off[d]) throw_err(CTOK_E_ARG, "offsets must be non-decreasing");
+  const uint64_t n_in = doc_off[n_docs];
+  if (n_in && !utf8) throw_err(CTOK_E_ARG, "null text");
+  DeviceState* ds = device_state(t, dev);
+  std::lock_guard<std::recursive_mutex> lk(ds->mu);
+  HIPTRY(hipSetDevice(dev));
+  hipStream_t s = ds->stream;
+  ds->pad_in_text.ensure(n_in + 16);
+  ds->pad_in_off.ensure(n_docs + 1);
+  if (n_in) HIPTRY(hipMemcpyAsync(ds->pad_in_text.p, utf8, n_in, hipMemcpyHostToDevice, s));
+  HIPTRY(hipMemsetAsync(ds->pad_in_text.p + n_in, 0, 16, s));
+  HIPTRY(hipMemcpyAsync(ds->pad_in_off.p, doc_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+  encode_device(t, ds, ds->pad_in_text.p, ds->pad_in_off.p, n_docs, n_in, nullptr, 0, nullptr, s, false, nullptr, true,
+                true);
+  DevicePretok r;
+  r.text = ds->last_norm ? ds->norm_text.p : ds->pad_in_text.p;
+  r.doc_off = ds->last_norm ? ds->norm_off.p : ds->pad_in_off.p;
+  r.pbits = ds->pbits.p;
+  r.n_bytes = ds->last_B;
+  r.n_docs = n_docs;
+  r.stream = s;
+  use(r);
 }
 }  // namespace ctok_host
 

@@ -3,7 +3,9 @@
 // Reference: InlBpeTrainer, src/trainer.rs (Complexity-ML/complexity-tokenizer v0.3.3).  This file
 // restates its control flow step by step; the O(words) work of every step runs on the GPU:
 //   count_batch / count_words (:207-285)   NFC + ByteLevel pre-tokenization on the GPU (the encode
-//                                          path's k_segment), word histogram on host threads
+//                                          path's k_segment), word histogram in a device hash
+//                                          table per chunk (wordcount.hip); CTOK_TRAIN_COUNT=host
+//                                          or a table overflow: the histogram on host threads
 //   init_vocab_bytelevel (:288-339)        host (alphabet ids in ascending code point order: the
 //                                          reference's HashSet order is randomly seeded)
 //   compute_initial_pairs (:341-367)       GPU pair histogram (trainer.hip k_count_pairs)
@@ -32,6 +34,7 @@
 #include "../../include/ctok_trainer.h"
 #include "host_common.h"
 #include "trainer_internal.h"
+#include "wordcount_internal.h"
 
 using namespace ctok_train;
 using ctok_host::throw_error;
@@ -55,6 +58,20 @@ struct DBuf {  // device buffer, grown on demand
     cap = 0;
     HIPT(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)));
     cap = n;
+  }
+  // ensure() that reports an allocation failure instead of throwing (the buffer is then empty)
+  bool try_ensure(size_t n) {
+    if (n <= cap) return true;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    if (hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
+      (void)hipGetLastError();  // (the failure is handled: leave no error behind for the next call)
+      p = nullptr;
+      return false;
+    }
+    cap = n;
+    return true;
   }
   ~DBuf() {
     if (p) (void)hipFree(p);
@@ -136,8 +153,17 @@ struct ctok_trainer {
   DBuf<int64_t> vals, out_vals;
   DBuf<unsigned long long> tok_freq;
   uint32_t mask = 0;
+  // word counting on the device (wordcount.hip): the chunk's table and its drained entries, kept
+  // across chunks and calls
+  DBuf<uint64_t> wc_keys, wc_off, wc_tmp;
+  DBuf<uint32_t> wc_vals, wc_used, wc_ctr, wc_cnt, wc_pos;
+  DBuf<uint8_t> wc_bytes;
+  hipEvent_t wc_ev[2] = {nullptr, nullptr};
+  ctok_trainer_count_info cstats{};  // of the last count() call
 
   ~ctok_trainer() {
+    for (auto& e : wc_ev)
+      if (e) (void)hipEventDestroy(e);
     if (pretok) ctok_destroy(pretok);
     if (s) (void)hipStreamDestroy(s);
   }
@@ -168,9 +194,18 @@ struct ctok_trainer {
   // longer text is a chunk by itself): one encode call is limited to 3.75 GiB and sizes its
   // workspace from its text, while count_words streams any amount (src/trainer.rs:265-285).
   void count(const uint8_t* utf8, const uint64_t* off, uint64_t n, std::unordered_map<std::string, uint32_t>& into) {
+    cstats = ctok_trainer_count_info{};
     if (!n) return;
     if (off[0] != 0) throw_error(CTOK_E_ARG, "offsets[0] must be 0");
     ensure_pretok();
+    const double t_start = now_ms();
+    struct Stop {  // (ms_host also when a chunk throws)
+      ctok_trainer_count_info& c;
+      double t0;
+      ~Stop() { c.ms_host = now_ms() - t0; }
+    } stop{cstats, t_start};
+    const char* mode = getenv("CTOK_TRAIN_COUNT");
+    const bool host_only = mode && !strcmp(mode, "host");
     uint64_t chunk = 256ull << 20;
     if (const char* e = getenv("CTOK_TRAIN_CHUNK_BYTES")) chunk = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
     std::vector<uint64_t> coff;
@@ -179,16 +214,129 @@ struct ctok_trainer {
       while (d1 < n && off[d1 + 1] - off[d0] <= chunk) d1++;
       coff.resize(d1 - d0 + 1);
       for (uint64_t i = d0; i <= d1; i++) coff[i - d0] = off[i] - off[d0];
-      count_chunk(utf8 + off[d0], coff.data(), d1 - d0, into);
+      cstats.chunks++;
+      if (host_only || !count_chunk_device(utf8 + off[d0], coff.data(), d1 - d0, into)) {
+        cstats.host_chunks++;
+        count_chunk(utf8 + off[d0], coff.data(), d1 - d0, into);
+      }
       d0 = d1;
     }
   }
 
+  // One chunk counted on the device: the pre-tokenizer's text and bitmap stay there, the words are
+  // counted into a hash table that refers into the text (wordcount.hip), and only the table's
+  // (word, count) entries come back.  Capacity: a power of two >= pieces / 2 (natural text has far
+  // fewer unique words than pieces), at most CTOK_TRAIN_COUNT_SLOTS when set; when a probe sequence
+  // runs out the chunk is counted again with >= 2 * pieces slots (unique words <= pieces, so that
+  // table is at most half full), and a chunk that overflows the largest table allowed, or whose
+  // table cannot be allocated, returns false with nothing added to `into`: the caller counts it on
+  // the host.
+  bool count_chunk_device(const uint8_t* utf8, const uint64_t* off, uint64_t n,
+                          std::unordered_map<std::string, uint32_t>& into) {
+    using namespace ctok_wc;
+    uint64_t slot_cap = 1ull << 31;
+    if (const char* e = getenv("CTOK_TRAIN_COUNT_SLOTS")) slot_cap = std::max<uint64_t>(2, std::min<uint64_t>(slot_cap, strtoull(e, nullptr, 10)));
+    auto pow2_in_cap = [&](uint64_t want) {
+      uint64_t c = 1024;
+      while (c < want && c < (1ull << 31)) c <<= 1;
+      while (c > slot_cap) c >>= 1;
+      return c;
+    };
+    bool ok = false;
+    ctok_host::pretokenize_device(pretok, device, utf8, off, n, [&](const ctok_host::DevicePretok& r) {
+      hipStream_t st = (hipStream_t)r.stream;
+      const Text x{r.text, r.pbits, (uint32_t)r.n_bytes, (uint32_t)((r.n_bytes + 31) / 32)};
+      if (!x.n_bytes) {
+        ok = true;
+        return;
+      }
+      for (auto& e : wc_ev)
+        if (!e) HIPT(hipEventCreate(&e));
+      uint32_t ctr[kNumCtr] = {0, 0, 0, 0};
+      wc_ctr.ensure(kNumCtr);
+      HIPT(hipMemsetAsync(wc_ctr.p, 0, kNumCtr * 4, st));
+      HIPT(hipEventRecord(wc_ev[0], st));
+      HIPT(launch_pieces(x, wc_ctr.p, st));
+      HIPT(hipEventRecord(wc_ev[1], st));
+      HIPT(hipMemcpyAsync(ctr, wc_ctr.p, kNumCtr * 4, hipMemcpyDeviceToHost, st));
+      HIPT(hipStreamSynchronize(st));
+      add_device_ms();
+      cstats.bytes_d2h += kNumCtr * 4;
+      const uint64_t pieces = ctr[kCtrPieces];
+      const uint32_t min_len = (uint32_t)std::min<uint64_t>(min_word_length, 0xFFFFFFFFull);
+      uint64_t cap = pow2_in_cap(pieces / 2);
+      for (int attempt = 0; attempt < 2; attempt++) {
+        // (no memory for the table, the larger one above all: the host walk counts the chunk)
+        if (!wc_keys.try_ensure(cap) || !wc_vals.try_ensure(cap) || !wc_used.try_ensure(cap)) break;
+        HIPT(hipEventRecord(wc_ev[0], st));
+        HIPT(hipMemsetAsync(wc_keys.p, 0xFF, cap * 8, st));
+        HIPT(hipMemsetAsync(wc_vals.p, 0, cap * 4, st));
+        HIPT(hipMemsetAsync(wc_ctr.p, 0, kNumCtr * 4, st));
+        const Table T{wc_keys.p, wc_vals.p, (uint32_t)(cap - 1), wc_used.p, wc_ctr.p};
+        HIPT(launch_count(x, T, min_len, st));
+        HIPT(hipEventRecord(wc_ev[1], st));
+        HIPT(hipMemcpyAsync(ctr, wc_ctr.p, kNumCtr * 4, hipMemcpyDeviceToHost, st));
+        HIPT(hipStreamSynchronize(st));
+        add_device_ms();
+        cstats.bytes_d2h += kNumCtr * 4;
+        if (!ctr[kCtrOverflow]) {
+          drain_chunk(x, T, ctr[kCtrUsed], st, into);
+          cstats.pieces += pieces;
+          cstats.words += ctr[kCtrWords];
+          cstats.unique_words += ctr[kCtrUsed];
+          ok = true;
+          break;
+        }
+        const uint64_t larger = pow2_in_cap(2 * pieces);
+        if (attempt == 1 || larger <= cap) break;
+        cap = larger;
+        cstats.rerun_chunks++;
+      }
+    });
+    return ok;
+  }
+
+  // ms_device += the span between the two events (both complete: the stream was synchronised)
+  void add_device_ms() {
+    float ms = 0;
+    HIPT(hipEventElapsedTime(&ms, wc_ev[0], wc_ev[1]));
+    cstats.ms_device += ms;
+  }
+
+  // the table's used slots -> (bytes, offsets, counts) on the device -> added into `into`
+  void drain_chunk(const ctok_wc::Text& x, const ctok_wc::Table& T, uint32_t n_used, hipStream_t st,
+                   std::unordered_map<std::string, uint32_t>& into) {
+    if (!n_used) return;
+    wc_off.ensure((uint64_t)n_used + 1);
+    wc_cnt.ensure(n_used);
+    wc_pos.ensure(n_used);
+    wc_tmp.ensure(ctok_wc::drain_tmp_elems(n_used));
+    wc_bytes.ensure(x.n_bytes);  // distinct words' first occurrences are disjoint pieces of the text
+    HIPT(hipEventRecord(wc_ev[0], st));
+    HIPT(ctok_wc::launch_drain(x, T, n_used, wc_bytes.p, wc_off.p, wc_cnt.p, wc_pos.p, wc_tmp.p, wc_tmp.cap, st));
+    HIPT(hipEventRecord(wc_ev[1], st));
+    std::vector<uint64_t> h_off((size_t)n_used + 1);
+    std::vector<uint32_t> h_cnt(n_used);
+    HIPT(hipMemcpyAsync(h_off.data(), wc_off.p, h_off.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPT(hipMemcpyAsync(h_cnt.data(), wc_cnt.p, h_cnt.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPT(hipStreamSynchronize(st));
+    add_device_ms();
+    const uint64_t nb = h_off[n_used];
+    if (nb > x.n_bytes) throw_error(CTOK_E_DEVICE, "word counting: drained more bytes than the text holds");
+    std::vector<char> h_bytes(nb);
+    if (nb) HIPT(hipMemcpyAsync(h_bytes.data(), wc_bytes.p, nb, hipMemcpyDeviceToHost, st));
+    HIPT(hipStreamSynchronize(st));
+    cstats.bytes_d2h += h_off.size() * 8 + h_cnt.size() * 4 + nb;
+    for (uint32_t i = 0; i < n_used; i++) into[std::string(h_bytes.data() + h_off[i], h_off[i + 1] - h_off[i])] += h_cnt[i];
+  }
+
+  // One chunk counted by the host walk (CTOK_TRAIN_COUNT=host, or the device table overflowed).
   void count_chunk(const uint8_t* utf8, const uint64_t* off, uint64_t n, std::unordered_map<std::string, uint32_t>& into) {
     std::vector<uint8_t> text;
     std::vector<uint64_t> noff;
     std::vector<uint32_t> pb;
-    ctok_host::pretokenize(pretok, device, utf8, off, n, text, noff, pb);
+    uint64_t d2h = 0;
+    ctok_host::pretokenize(pretok, device, utf8, off, n, text, noff, pb, &d2h);
     auto is_start = [&](uint64_t g) { return (pb[g >> 5] >> (g & 31)) & 1u; };
     const unsigned nth = n < 64 ? 1u : std::min(16u, ctok_host::usable_cpus());
     std::vector<std::unordered_map<std::string, uint32_t>> part(nth);
@@ -209,6 +357,10 @@ struct ctok_trainer {
     for (auto& x : th) x.join();
     for (auto& m : part)
       for (auto& kv : m) into[kv.first] += kv.second;
+    for (uint32_t v : pb) cstats.pieces += (uint64_t)__builtin_popcount(v);
+    for (auto& m : part)
+      for (auto& kv : m) cstats.words += kv.second;
+    cstats.bytes_d2h += d2h;
   }
 
   // train_from_word_freqs (src/trainer.rs:231-243) on raw-byte words
@@ -562,6 +714,42 @@ int ctok_trainer_initial_pairs(const ctok_trainer* tr, uint32_t* a, uint32_t* b,
       b[i] = (uint32_t)tr->initial[i].first;
       count[i] = tr->initial[i].second;
     }
+  });
+}
+
+int ctok_trainer_word_counts(const ctok_trainer* tr, int accumulator, uint8_t* bytes, uint64_t cap_bytes,
+                             uint64_t* word_off, uint32_t* freqs, uint64_t cap_words, uint64_t* n_words,
+                             uint64_t* n_bytes) {
+  return ctok_host::run_guarded([&] {
+    if (!tr || !n_words || !n_bytes) throw_error(CTOK_E_ARG, "null argument");
+    const auto& m = accumulator ? tr->acc : tr->local;
+    std::vector<std::pair<std::string, uint32_t>> v(m.begin(), m.end());
+    std::sort(v.begin(), v.end());
+    uint64_t nb = 0;
+    for (const auto& kv : v) nb += kv.first.size();
+    *n_words = v.size();
+    *n_bytes = nb;
+    if (cap_words < v.size() || cap_bytes < nb) return;
+    if (!word_off) {  // (the sizing call when there are no counts)
+      if (!v.empty()) throw_error(CTOK_E_ARG, "null argument");
+      return;
+    }
+    if ((v.size() && !freqs) || (nb && !bytes)) throw_error(CTOK_E_ARG, "null argument");
+    uint64_t o = 0;
+    for (size_t i = 0; i < v.size(); i++) {
+      word_off[i] = o;
+      freqs[i] = v[i].second;
+      std::memcpy(bytes + o, v[i].first.data(), v[i].first.size());
+      o += v[i].first.size();
+    }
+    word_off[v.size()] = o;
+  });
+}
+
+int ctok_trainer_count_stats(const ctok_trainer* tr, ctok_trainer_count_info* out) {
+  return ctok_host::run_guarded([&] {
+    if (!tr || !out) throw_error(CTOK_E_ARG, "null argument");
+    *out = tr->cstats;
   });
 }
 

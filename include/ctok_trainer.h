@@ -3,7 +3,8 @@
  * Drop-in for the reference's PyO3 class `complexity_tokenizer.Trainer`
  * (Complexity-ML/complexity-tokenizer v0.3.3, src/bindings/trainers.rs:10-92, registered at
  * src/lib.rs:50) over `InlBpeTrainer` (src/trainer.rs).  Word counting pre-tokenizes on the GPU
- * (NFC + ByteLevel, the encode path's k_segment) and counts words on the host; the pair histogram
+ * (NFC + ByteLevel, the encode path's k_segment) and counts the words on the GPU too (a device hash
+ * table per chunk; only its (word, count) entries come back to the host); the pair histogram
  * (compute_initial_pairs, src/trainer.rs:341-367) and every merge's pass over the words with its
  * pair-count deltas (apply_merge_incremental, :522-590) run on the GPU; the INL-scored heap
  * (build_heap / learn_merges_heap, :369-520) runs on the host in f32 exactly as the reference.
@@ -88,6 +89,32 @@ int ctok_trainer_initial_pairs(const ctok_trainer* tr, uint32_t* a, uint32_t* b,
 
 /* Milliseconds of the last training spent in GPU pair counting / merge application / host heap. */
 int ctok_trainer_timing(const ctok_trainer* tr, double* ms_pairs, double* ms_merges, double* ms_heap);
+
+/* Extension (the reference keeps its word counts private): the current word counts of the
+ * accumulator (accumulator = 1) or of train_from_iterator / train(files) (0), sorted by the words'
+ * raw (unmapped) bytes: word i = bytes[word_off[i] .. word_off[i + 1]) with count freqs[i].
+ * Always sets *n_words and *n_bytes; the arrays (word_off: cap_words + 1 entries) are filled only
+ * when cap_words >= *n_words and cap_bytes >= *n_bytes, so call once with zero capacities for the
+ * sizes and once more with the buffers. */
+int ctok_trainer_word_counts(const ctok_trainer* tr, int accumulator, uint8_t* bytes, uint64_t cap_bytes,
+                             uint64_t* word_off, uint32_t* freqs, uint64_t cap_words, uint64_t* n_words,
+                             uint64_t* n_bytes);
+
+/* Extension: what the last ctok_trainer_count call did.  Its texts are counted in chunks
+ * (CTOK_TRAIN_CHUNK_BYTES); a chunk is counted on the device, or by the host walk when
+ * CTOK_TRAIN_COUNT=host is set or it overflowed the largest device table allowed. */
+typedef struct ctok_trainer_count_info {
+  uint64_t pieces;        /* pre-tokenized pieces seen */
+  uint64_t words;         /* pieces of >= min_word_length bytes: the sum of the counts added */
+  uint64_t unique_words;  /* (word, count) entries drained from the device table, summed over chunks */
+  uint64_t chunks;
+  uint64_t host_chunks;   /* chunks counted by the host walk */
+  uint64_t rerun_chunks;  /* chunks counted a second time on the device with a larger table */
+  uint64_t bytes_d2h;     /* bytes copied device -> host for counting (not the pre-tokenizer's own status words) */
+  double ms_device;       /* HIP-event time of the counting and drain kernels (0 for host chunks) */
+  double ms_host;         /* wall time of the whole ctok_trainer_count call */
+} ctok_trainer_count_info;
+int ctok_trainer_count_stats(const ctok_trainer* tr, ctok_trainer_count_info* out);
 
 #ifdef __cplusplus
 }

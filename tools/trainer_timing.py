@@ -3,9 +3,16 @@
 merge passes on the GPU, csrc/trainer.hip) against the C restatement of the reference's per-merge
 work (oracle/trainer_ref.c: apply_merge_incremental + build_heap every 100 merges,
 /root/reference/src/trainer.rs:369-405, :519-588) on the same words and the same merge sequence.
-Prints one JSON line.   usage: python tools/trainer_timing.py [n_docs] [vocab_size]"""
+Prints one JSON line.   usage: python tools/trainer_timing.py [n_docs] [vocab_size]
+
+Counting section:       usage: python tools/trainer_timing.py count [c2|c4] [n_docs] [runs]
+Word counting (Trainer.count_batch's native call) of the same texts on the device path (the default,
+csrc/wordcount.hip) and on the host walk (CTOK_TRAIN_COUNT=host, the code before the device path),
+each variant in a fresh child process: 2 warm-up calls, then `runs` timed calls on a new Trainer
+each; count_stats of every timed call, their medians, and host / device of ms_host."""
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -14,6 +21,57 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "complexity-tokenizer_amd")]
 
 from complexity_tokenizer import Trainer  # noqa: E402
 from datagen import corpus  # noqa: E402
+
+
+def _count_child(kind, n_docs, runs):
+    from complexity_tokenizer import _native as _n
+    if kind == "c2":
+        text, off = corpus.corpus_c2(n_docs, seed=31)
+    else:
+        text, off = corpus.corpus_c4_range(0, n_docs)
+    out = []
+    for k in range(2 + runs):
+        t = Trainer()
+        rc = _n.lib.ctok_trainer_count(t._h, text.ctypes.data, off.ctypes.data, len(off) - 1, 1)
+        assert rc == 0, _n.last_error()
+        if k >= 2:
+            out.append(t.count_stats())
+    print(json.dumps({"bytes": int(off[-1]), "docs": len(off) - 1, "runs": out}), flush=True)
+
+
+def _count_section(kind, n_docs, runs):
+    res = {}
+    for name, mode in (("host", "host"), ("device", None)):
+        env = dict(os.environ)
+        env.pop("CTOK_TRAIN_COUNT", None)
+        if mode:
+            env["CTOK_TRAIN_COUNT"] = mode
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--count-child", kind, str(n_docs), str(runs)],
+                           env=env, check=True, capture_output=True, text=True)
+        res[name] = json.loads(r.stdout.strip().splitlines()[-1])
+
+    def med(name, key):
+        v = sorted(x[key] for x in res[name]["runs"])
+        return v[len(v) // 2]
+
+    summary = {name: {k: (round(med(name, k), 3) if k.startswith("ms_") else med(name, k)) for k in res[name]["runs"][0]}
+               for name in res}
+    print(json.dumps({
+        "what": "word counting of %d %s docs (%d bytes): medians of %d calls after 2 warm-up calls, per path"
+                % (res["device"]["docs"], kind.upper(), res["device"]["bytes"], runs),
+        "host": summary["host"], "device": summary["device"],
+        "ms_host_ratio_host_over_device": round(summary["host"]["ms_host"] / max(summary["device"]["ms_host"], 1e-9), 2),
+        "runs": {name: res[name]["runs"] for name in res},
+    }), flush=True)
+
+
+if len(sys.argv) > 1 and sys.argv[1] in ("count", "--count-child"):
+    _kind = sys.argv[2] if len(sys.argv) > 2 else "c2"
+    _nd = int(sys.argv[3]) if len(sys.argv) > 3 else 20_000
+    _runs = int(sys.argv[4]) if len(sys.argv) > 4 else 5
+    (_count_child if sys.argv[1] == "--count-child" else _count_section)(_kind, _nd, _runs)
+    sys.exit(0)
+
 from oracle import trainer_c, trainer_ref  # noqa: E402
 
 n_docs = int(sys.argv[1]) if len(sys.argv) > 1 else 20_000
