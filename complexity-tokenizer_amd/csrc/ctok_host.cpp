@@ -350,6 +350,7 @@ struct ctok {
   bool proper = true;
   bool compact = false;
   bool narrow = false;  // every vocab id < 2^16
+  bool short_packed = false;  // narrow, and every narrow-table value fits the packed 16-slot tier (Tables::short_packed)
   bool ids16 = false;   // every id encode can emit (vocab and added tokens) < 2^16: 16-bit ids on PCIe
   // decode (src/huggingface/mod.rs:710-747): decoder kind, per-id decoded bytes
   int decoder = 1;                  // 1 ByteLevel, 0 raw concatenation (unknown decoder type), -1 unsupported
@@ -1192,6 +1193,23 @@ void load_root(ctok* t, const ctj::Value& root) {
       const uint32_t r = it->second;
       t->pair0[a * 256 + b] = t->compact ? (r < valid_new.size() ? valid_new[r] : kPanicVal) : r;
     }
+  // The packed 16-slot tier of k_bpe_short (merge16_hd.h) keeps table values as u16 with 0xFFFF
+  // for "none": every value it can see -- the byte-pair table, the narrow global table, the narrow
+  // hot table -- must be below 0xFFFF, and none may be one whose lookup panics (the tier does not
+  // check for those).  Compact tables (value = new id) of a narrow vocabulary without panicking
+  // entries qualify; the tier is built for compact tables only.
+  if (t->narrow && t->compact) {
+    auto fits = [&](uint32_t v) { return v < 0xFFFFu; };  // (kPanicVal is above it)
+    bool ok = true;
+    for (uint32_t v : t->pair0) ok = ok && (v == kNoRank || fits(v));
+    for (uint64_t e : t->merge16) ok = ok && (e == kEmpty || fits((uint32_t)(e >> 32)));
+    for (uint32_t i = 0; i < kHotU64; i++) {
+      const uint64_t e = t->lds16_image[i];
+      ok = ok && (e == kEmpty || fits((uint32_t)(e >> 32)));
+    }
+    t->short_packed = ok;
+  }
+  if (lt) fprintf(stderr, "[ctok load] narrow %d compact %d short_packed %d\n", (int)t->narrow, (int)t->compact, (int)t->short_packed);
 
   lap("proper+pair0");
   // whole-piece table: every vocab entry of <= 8 raw bytes whose own BPE is that single token
@@ -1477,6 +1495,10 @@ DeviceState* device_state(ctok* t, int device) {
   tb.proper = (t->proper && !getenv("CTOK_FORCE_IMPROPER")) ? 1 : 0;
   tb.compact = t->compact ? 1 : 0;
   tb.narrow = (t->narrow && !getenv("CTOK_FORCE_WIDE_SLOTS")) ? 1 : 0;
+  {  // CTOK_SHORT_PACKED=0: the 16 + 16 register tier on every table (A/B arm; the tests run both)
+    const char* pk = getenv("CTOK_SHORT_PACKED");
+    tb.short_packed = (tb.narrow && t->short_packed && !(pk && atoi(pk) == 0)) ? 1 : 0;
+  }
   tb.all_bytes = std::all_of(t->byte2id, t->byte2id + 256, [](int32_t v) { return v >= 0; }) ? 1 : 0;
   tb.dbg = getenv("CTOK_DBG_MODE") ? (uint32_t)atoi(getenv("CTOK_DBG_MODE")) : 0;
   DeviceState* r = ds.get();

@@ -220,6 +220,8 @@ struct Tables {            // device pointers, owned by the host runtime
                             // (bits 0-15) and the longest right side of one it is the left side of
   uint32_t compact;         // 1: entry values are new ids (strictly increasing in rank), else ranks
   uint32_t narrow;          // 1: every vocab id < 2^16 (the merge passes keep the last tier's tokens as u16 in LDS)
+  uint32_t short_packed;    // 1 (narrow and compact only): every value of pair0, merge16 and the narrow LDS image is
+                            // < 0xFFFF and none panics, so k_bpe_short's 16-slot tier keeps values as u16 pairs (merge16_hd.h)
   uint32_t dbg;             // debug mode (CTOK_DBG_MODE), 0 in production
   uint32_t all_bytes;       // 1: every byte's char is in the vocab (no piece can have a dropped byte)
 };

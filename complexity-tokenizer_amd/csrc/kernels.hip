@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "ctok_internal.h"
+#include "merge16_hd.h"
 #include "seg_lane.h"
 
 namespace ctok_dev {
@@ -1401,16 +1402,12 @@ __device__ __forceinline__ bool merge_slots(const Tables& t, const PairLds& P, u
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
 
 // out_of(m) returns where the piece's m ids go (called once, after the last merge).
+// merge_lds8_run: the loop on a state already in LDS (merge_lds8 stores it from u32 registers,
+// the packed 16-slot tier from its u16 pairs).
 template <bool COMPACT, bool HOT, uint32_t NT, typename OutOf>
-__device__ __forceinline__ uint32_t merge_lds8(const Tables& t, const PairLds& P, const uint32_t* tk, const uint32_t* rk,
-                                               uint32_t m, lds_u32* s_key, lds_u16* s_tok, uint32_t* err,
-                                               OutOf&& out_of) {
+__device__ __forceinline__ uint32_t merge_lds8_run(const Tables& t, const PairLds& P, uint32_t m, lds_u32* s_key,
+                                                   lds_u16* s_tok, uint32_t* err, OutOf&& out_of) {
   const uint32_t tid = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    s_key[k * NT + tid] = (uint32_t)k + 1 < m ? (rk[k] << 3) | (uint32_t)k : ~0u;
-    s_tok[k * NT + tid] = (uint16_t)tk[k];
-  }
   // live slots, with a sentinel at bit 8 (so every "next live" search finds a bit)
   uint32_t lv = ((1u << m) - 1u) | 0x100u;
   for (;;) {
@@ -1448,6 +1445,60 @@ __device__ __forceinline__ uint32_t merge_lds8(const Tables& t, const PairLds& P
   return m;
 }
 
+template <bool COMPACT, bool HOT, uint32_t NT, typename OutOf>
+__device__ __forceinline__ uint32_t merge_lds8(const Tables& t, const PairLds& P, const uint32_t* tk, const uint32_t* rk,
+                                               uint32_t m, lds_u32* s_key, lds_u16* s_tok, uint32_t* err,
+                                               OutOf&& out_of) {
+  const uint32_t tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    s_key[k * NT + tid] = (uint32_t)k + 1 < m ? (rk[k] << 3) | (uint32_t)k : ~0u;
+    s_tok[k * NT + tid] = (uint16_t)tk[k];
+  }
+  return merge_lds8_run<COMPACT, HOT, NT>(t, P, m, s_key, s_tok, err, out_of);
+}
+
+// The packed 16-slot tier (merge16_hd.h) over the pass's tables: the two lookups of a step as
+// Probe<true, HOT>, their loads in flight while the step moves its slots.  Compact tables only
+// (Tables::short_packed): a value is the merged token's id.
+template <bool HOT>
+struct Lookup16 {
+  const Tables& t;
+  const PairLds& P;
+  uint32_t* err;
+  Probe<true, HOT> pl, pr;
+  bool has_l = false, has_r = false;
+  __device__ __forceinline__ uint32_t new_id(uint32_t v) const { return v; }
+  __device__ __forceinline__ void start(uint32_t L, uint32_t nid, uint32_t R, bool hl, bool hr) {
+    has_l = hl;
+    has_r = hr;
+    pl.start(t, P, L, nid, hl);
+    pr.start(t, P, nid, R, hr);
+  }
+  // (kNoRank's low 16 bits are m16::kNone; every other value is < 0xFFFF: Tables::short_packed)
+  __device__ __forceinline__ void finish(uint32_t& rl, uint32_t& rr) {
+    rl = (has_l ? pl.finish(t, err) : kNoRank) & 0xFFFFu;
+    rr = (has_r ? pr.finish(t, err) : kNoRank) & 0xFFFFu;
+  }
+};
+
+template <int K0, int K1, uint32_t NT>
+__device__ __forceinline__ void lds8_store_packed(const uint32_t (&T)[8], const uint32_t (&R)[8], lds_u32* s_key,
+                                                  lds_u16* s_tok) {
+  if constexpr (K0 < K1) {
+    s_key[K0 * NT + threadIdx.x] = m16::lds8_key<K0>(R);
+    s_tok[K0 * NT + threadIdx.x] = (uint16_t)m16::half<K0>(T);
+    lds8_store_packed<K0 + 1, K1, NT>(T, R, s_key, s_tok);
+  }
+}
+template <int K0, int K1>
+__device__ __forceinline__ void store_packed_ids(const uint32_t (&T)[8], uint32_t m, uint32_t* out) {
+  if constexpr (K0 < K1) {
+    if ((uint32_t)K0 < m) out[K0] = m16::half<K0>(T);
+    store_packed_ids<K0 + 1, K1>(T, m, out);
+  }
+}
+
 // Workgroup-shared scratch of a merge pass.
 template <uint32_t SORTCAP, int KT = 64>
 struct PassLds {
@@ -1464,7 +1515,10 @@ struct PassLds {
 // work, so a workgroup that finds only empty lists never reads the 32..96 KiB image (`loaded`
 // is shared by the passes of one kernel).
 // L8: the <= 8-token tier runs in LDS (merge_lds8, narrow vocabularies; s_key / s_tok its state).
-template <int N, bool COMPACT, bool HOT, uint32_t NT, uint32_t SORTCAP, bool L8 = false, int KT = 64, typename Load>
+// PK (N = 16, L8): the 16-slot tier keeps tokens and values as u16 pairs (merge16_hd.h; tables
+// whose values all fit, Tables::short_packed).
+template <int N, bool COMPACT, bool HOT, uint32_t NT, uint32_t SORTCAP, bool L8 = false, int KT = 64, bool PK = false,
+          typename Load>
 __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const PairLds& P, const int32_t* s_b2id,
                                            PassLds<SORTCAP, KT>& S, bool& loaded, Load&& load,
                                            lds_u32* s_key = nullptr, lds_u16* s_tok = nullptr) {
@@ -1551,6 +1605,62 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
         const uint32_t s = tile * kTile + (e & 0xFFFu);
         const uint32_t o = ent_ord(e);
         const uint32_t n = ent_len(e);
+        if constexpr (PK) {
+          static_assert(N == 16 && L8 && COMPACT, "the packed tier is the 9..16 B pass's, ahead of merge_lds8, on compact tables");
+          // packed tokens straight from the byte -> id table, packed values from the byte-pair
+          // table (no entry of it panics and every value fits 16 bits: Tables::short_packed;
+          // kNoRank's low half is m16::kNone)
+          uint32_t T[8], R[8], bytes[N];
+          bool missing = false;
+#pragma unroll
+          for (int k = 0; k < N; k++) bytes[k] = byte_of(wv[k >> 2], k);
+#pragma unroll
+          for (int d = 0; d < 8; d++) {
+            const int32_t i0 = s_b2id[bytes[2 * d]], i1 = s_b2id[bytes[2 * d + 1]];
+            missing |= (((uint32_t)(2 * d) < n) & (i0 < 0)) | (((uint32_t)(2 * d + 1) < n) & (i1 < 0));
+            T[d] = m16::pack2((uint32_t)i0, (uint32_t)i1);
+          }
+          if (missing) {  // a byte char absent from the vocab is dropped: generic path
+            hook();
+            const uint32_t mi = atomicAdd(&w.counters[4], 1u);
+            if (mi < w.mid_cap)
+              w.mid_list[mi] = (uint64_t)s | ((uint64_t)o << 32) | ((uint64_t)n << 48);
+            else
+              atomicOr(&w.counters[kCtrOverflow], 1u);
+            return;
+          }
+          {
+            uint32_t v[N];
+#pragma unroll
+            for (int k = 0; k < N - 1; k++) v[k] = t.pair0[(bytes[k] << 8) | bytes[k + 1]];
+            v[N - 1] = kNoRank;
+#pragma unroll
+            for (int k = 0; k < N - 1; k++) v[k] = (uint32_t)k + 1 < n ? v[k] : kNoRank;
+#pragma unroll
+            for (int d = 0; d < 8; d++) R[d] = m16::pack2(v[2 * d], v[2 * d + 1]);
+          }
+          uint32_t m = n;
+          Lookup16<HOT> lk{t, P, err};
+          const bool more = m16::tier(T, R, m, 8u, lk);
+          hook();
+          uint32_t pos = 0;
+          auto out_of = [&](uint32_t mm) {
+            pos = atomicAdd(&S.tsum[kt], mm);
+            return w.scratch + (size_t)tile * kTileSlots + pos;
+          };
+          if (more) {
+            lds8_store_packed<0, 8, NT>(T, R, s_key, s_tok);
+            m = merge_lds8_run<COMPACT, HOT, NT>(t, P, m, s_key, s_tok, err, out_of);
+          } else {
+            store_packed_ids<0, N>(T, m, out_of(m));
+          }
+          CTOK_CHECK_REC(m >= 1 && m <= n && pos + m <= (uint32_t)kTileSlots && o < (uint32_t)kTileSlots,
+                         "[ctok check] packed class pass tile %u: record m=%u n=%u pos=%u ordinal=%u\n", tile, m, n, pos, o);
+          w.mrec[(size_t)tile * kTileSlots + o] = rec_short(m, pos);
+          st_bytes += n;
+          st_ids += m;
+          return;
+        }
         uint32_t tk[N], rk[N];
         bool missing = false;
         {
@@ -1744,8 +1854,10 @@ template <bool NARROW> struct ShortCfg {
 // tiles per chunk measured 3% slower, profiles/r02/v30_ab_short_kt128.txt)
 constexpr int kShortKT = 64;
 
-template <bool COMPACT, bool NARROW>
+// PK16 (narrow compact tables with Tables::short_packed): the 9..16 B pass's 16-slot tier on u16 pairs.
+template <bool COMPACT, bool NARROW, bool PK16 = false>
 __global__ __launch_bounds__(1024) void k_bpe_short(Work w, Tables t, uint32_t passes) {
+  static_assert((NARROW && COMPACT) || !PK16, "the packed tier needs the narrow tables and compact values");
   if (w.report && blockIdx.x == 0 && threadIdx.x < 64) write_report(w);  // (k_report's work: see there)
   if (spec_failed(w)) return;
   constexpr uint32_t NT = ShortCfg<NARROW>::NT;
@@ -1770,7 +1882,7 @@ __global__ __launch_bounds__(1024) void k_bpe_short(Work w, Tables t, uint32_t p
   if (passes & 1u)
     class_pass<8, COMPACT, true, NT, ShortCfg<NARROW>::SORTCAP, NARROW, kShortKT>(w, t, P, s_b2id, S, loaded, load, sk, st);
   if (passes & 2u)
-    class_pass<16, COMPACT, true, NT, ShortCfg<NARROW>::SORTCAP, NARROW, kShortKT>(w, t, P, s_b2id, S, loaded, load, sk, st);
+    class_pass<16, COMPACT, true, NT, ShortCfg<NARROW>::SORTCAP, NARROW, kShortKT, PK16>(w, t, P, s_b2id, S, loaded, load, sk, st);
   WgRec::end(w.wgrec, 0, loaded ? 1u : 0u);
 }
 
@@ -2005,23 +2117,26 @@ static hipError_t launch_mid(const Work& w, const Tables& t, hipStream_t s, cons
   return t.narrow ? launch_mid_t<C, CLS, true>(w, t, s, x) : launch_mid_t<C, CLS, false>(w, t, s, x);
 }
 
-template <bool C, bool NW>
+template <bool C, bool NW, bool PK = false>
 static hipError_t launch_short_t(const Work& w, const Tables& t, hipStream_t s, const Lx& x) {
   static LdsAttr attr;
-  HIPCHK(lds_attr_once(attr, (const void*)k_bpe_short<C, NW>, kLdsImageBytes));
+  HIPCHK(lds_attr_once(attr, (const void*)k_bpe_short<C, NW, PK>, kLdsImageBytes));
   if (!w.n_tiles) return hipSuccess;
   // (Work::short_wgs: fewer workgroups than CUs leave CUs to the side stream's passes from the start)
   const uint32_t grid = min((w.n_tiles + w.unit - 1) / w.unit, w.short_wgs ? min(w.short_wgs, w.n_cus) : w.n_cus);
   if (t.dbg == 30) {
-    k_bpe_short<C, NW><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 1u);
-    k_bpe_short<C, NW><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 2u);
+    k_bpe_short<C, NW, PK><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 1u);
+    k_bpe_short<C, NW, PK><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 2u);
   } else {
-    launch_lx(x, k_bpe_short<C, NW>, grid, ShortCfg<NW>::NT, kLdsImageBytes, s, w, t, 3u);
+    launch_lx(x, k_bpe_short<C, NW, PK>, grid, ShortCfg<NW>::NT, kLdsImageBytes, s, w, t, 3u);
   }
   return hipGetLastError();
 }
 template <bool C>
 static hipError_t launch_short(const Work& w, const Tables& t, hipStream_t s, const Lx& x) {
+  if constexpr (C) {
+    if (t.narrow && t.short_packed) return launch_short_t<true, true, true>(w, t, s, x);
+  }
   return t.narrow ? launch_short_t<C, true>(w, t, s, x) : launch_short_t<C, false>(w, t, s, x);
 }
 
