@@ -287,6 +287,19 @@ class Tokenizer:
         """Extension (diagnostic): added tokens the GPU split runs on (include/ctok.h)."""
         return int(_n.lib.ctok_num_piece_added_tokens(self._h))
 
+    @property
+    def table_props(self) -> dict:
+        """Extension (diagnostic, include/ctok.h ctok_table_props): which 16-bit id variants this
+        tokenizer selects -- the load-time properties (narrow, compact, short_packed, ids16) as
+        bools, and for self.device the two built into its device tables after the environment
+        switches (dev_narrow, dev_short_packed) and the last encode call's piece-record and wire
+        formats (last_rec16, last_wire16); those four are None until such a call has run."""
+        tp = _n.TableProps()
+        rc = _n.lib.ctok_get_table_props(self._h, int(self.device), ctypes.byref(tp))
+        if rc != _n.CTOK_OK:
+            _raise(rc)
+        return {k: None if getattr(tp, k) < 0 else bool(getattr(tp, k)) for k, _ in tp._fields_}
+
     # ------------------------------------------------------------------ encode
     def encode_packed(self, text: np.ndarray, off: np.ndarray, timing: bool = False):
         """Extension: encode a packed batch (uint8 UTF-8 buffer, uint64 offsets[D+1]) and return

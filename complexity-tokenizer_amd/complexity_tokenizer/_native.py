@@ -114,6 +114,11 @@ class Tables(ctypes.Structure):  # include/ctok.h ctok_tables
                 ("nfc", ctypes.c_int), ("add_prefix_space", ctypes.c_int)]
 
 
+class TableProps(ctypes.Structure):  # include/ctok.h ctok_table_props
+    _fields_ = [(k, ctypes.c_int) for k in ("narrow", "compact", "short_packed", "ids16", "dev_narrow",
+                                            "dev_short_packed", "last_rec16", "last_wire16")]
+
+
 class TrainerConfig(ctypes.Structure):  # include/ctok_trainer.h
     _fields_ = [("vocab_size", ctypes.c_uint64), ("min_frequency", ctypes.c_uint32),
                 ("min_word_length", ctypes.c_uint64), ("inl_alpha", ctypes.c_float), ("inl_beta", ctypes.c_float),
@@ -150,6 +155,7 @@ SIGS = {
     "ctok_ids_bound": (_u64, [_p, _u64, _u64]),
     "ctok_num_piece_added_tokens": (_u64, [_p]),
     "ctok_piece_can_contain": (ctypes.c_int, [ctypes.c_char_p, _sz]),
+    "ctok_get_table_props": (ctypes.c_int, [_p, ctypes.c_int, ctypes.POINTER(TableProps)]),
     "ctok_encode_batch": (ctypes.c_int, [_p, _p, _p, _u64, _p, _u64, _p, ctypes.POINTER(Exec), ctypes.POINTER(Stats)]),
     "ctok_encode_batch_device": (ctypes.c_int, [_p, _p, _p, _u64, _u64, _p, _u64, _p, _u64p, ctypes.POINTER(Exec),
                                                 ctypes.POINTER(Stats)]),

@@ -265,6 +265,7 @@ struct DeviceState {
   bool last_norm = false;  // the last encode ran on norm_text / norm_off (last_B bytes)
   bool last_mid_side = false;  // the last encode ran the 17..32 B pass on the side stream
   uint64_t last_B = 0;
+  int last_rec16 = -1, last_wire16 = -1;  // diagnostics (ctok_get_table_props): the last encode's piece records / wire format
   // decode: tables (uploaded on first use), workspace, events
   bool dec_ready = false;
   DevBuf<uint32_t> dec_ent;
@@ -1795,6 +1796,7 @@ uint64_t encode_device(ctok* t, DeviceState* ds, const uint8_t* d_text, const ui
   // piece records: u16 when every id a whole-piece probe can return is below 0xFFFF
   static const bool rec32_env = getenv("CTOK_REC32") != nullptr;
   w.rec16 = (t->narrow && !rec32_env) ? 1u : 0u;
+  ds->last_rec16 = (int)w.rec16;
   ds->prec.ensure(nt * kTileSlots * (w.rec16 ? 1 : 2) + 16);
   ds->mrec.ensure(nt * kTileSlots + 8);
   ds->pdoc.ensure(nt * (kTileSlots / 32) + 8);
@@ -2340,6 +2342,7 @@ RangeOut encode_host_range(ctok* t, DeviceState* ds, const uint8_t* text, const 
   // fresh output pages on several threads); the link is the E2E bound (56 GB/s for both
   // directions together), and this moves 2 B per id instead of 4
   const bool w16 = t->ids16 && !getenv("CTOK_WIRE32");
+  ds->last_wire16 = w16 ? 1 : 0;
   auto drain = [&](size_t c) {
     HIPTRY(hipSetDevice(ds->device));
     const int k = (int)(c & 1);
@@ -2738,6 +2741,22 @@ int ctok_special_token(const ctok* t, uint64_t i, char* buf, size_t cap, size_t*
 }
 
 uint64_t ctok_num_piece_added_tokens(const ctok* t) { return t ? t->at_id.size() : 0; }
+
+int ctok_get_table_props(const ctok* tc, int device, ctok_table_props* out) {
+  if (!tc || !out) return fail(CTOK_E_ARG, "null argument");
+  ctok* t = const_cast<ctok*>(tc);
+  *out = ctok_table_props{t->narrow, t->compact, t->short_packed, t->ids16, -1, -1, -1, -1};
+  std::lock_guard<std::mutex> lk(t->dev_mu);
+  auto it = t->devs.find(device);
+  if (it != t->devs.end()) {
+    const DeviceState& ds = *it->second;
+    out->dev_narrow = (int)ds.t.narrow;
+    out->dev_short_packed = (int)ds.t.short_packed;
+    out->last_rec16 = ds.last_rec16;
+    out->last_wire16 = ds.last_wire16;
+  }
+  return CTOK_OK;
+}
 
 int ctok_piece_can_contain(const uint8_t* raw, size_t len) {
   if (!raw && len) return fail(CTOK_E_ARG, "null argument");

@@ -75,9 +75,10 @@ __host__ __device__ inline uint32_t long_ord(uint64_t e) { return (uint32_t)(e >
 __host__ __device__ inline uint32_t long_len(uint64_t e) { return (uint32_t)(e >> 44) & 0x7FFFFu; }
 
 // Piece records.  k_segment writes one per piece into prec[tile][j]: the whole-piece probe's id,
-// or kRecMerged (all ones) when a later pass produces the piece's ids -- u16 when every id the
-// tokenizer emits is below 0xFFFF (Work::rec16), else u32 -- and the piece's doc-start bit into
-// pdoc.  The merged pieces of a tile are numbered in piece order (their ordinal, carried by the
+// or kRecMerged (all ones) when a later pass produces the piece's ids -- u16 when every
+// model-vocab id is below 0xFFFF (Work::rec16; a probe returns vocabulary ids only, an added
+// token's id reaches the output through scratch / lids as u32), else u32 -- and the piece's
+// doc-start bit into pdoc.  The merged pieces of a tile are numbered in piece order (their ordinal, carried by the
 // list entries); the pass that finishes the tile's k-th merged piece writes mrec[tile][k] (u32):
 //   count | pos << 16       <= 64 B (register passes, generic pass): ids at
 //                           scratch[tile * kTileSlots + pos ..] (pos: a slot of the tile's region

@@ -2,9 +2,10 @@
 // register tier it replaces (kernels.hip merge_slots<16>: 16 + 16 u32 slots, the lowest
 // (value, position) pair merges, the slots right of it shift left, the two new pairs are looked
 // up).  Pair values come from a stub lookup.  Prints "ok" and exits 0, else says what differed.
-//   directed: every m in 9..16 x every merge position x values {0, 5, 0xFFFE} x neighbours with
-//             and without a value; ties of the lowest value at every pair of positions; tokens
-//             0 and 0xFFFE, dead slots 0xFFFF
+//   directed: every m in 9..16 x every merge position x values {0, 5, 0xFFFD, 0xFFFE} x neighbours
+//             with and without a value; ties of the lowest value at every pair of positions; tokens
+//             0, 0xFFFD and 0xFFFE (the two largest ids of a narrow table, next to the 0xFFFF of
+//             "none" and of dead slots)
 //   random:   full merge sequences from 9..16 tokens down to <= 8 (or until nothing merges), the
 //             state compared after every step, then the hand-off encoding of the 8-slot tier
 #include <cstdint>
@@ -21,12 +22,13 @@ constexpr uint32_t kDead = 0xFFFFFFFFu;
 // The stub table: value of pair (a, b) (< 0xFFFF) or kNoRank; new id of a value.
 struct Stub {
   uint32_t seed = 0;
-  int mode = 0;  // 0: hashed values; 1: every pair none; 2: every pair value 0; 3: every pair 0xFFFE
+  int mode = 0;  // 0: hashed values; 1: every pair none; 2: every pair value 0; 3: every pair 0xFFFE; 4: 0xFFFD
   bool compact = true;
   uint32_t value(uint32_t a, uint32_t b) const {
     if (mode == 1) return kNoRank;
     if (mode == 2) return 0;
     if (mode == 3) return 0xFFFEu;
+    if (mode == 4) return 0xFFFDu;
     uint32_t h = (a * 0x9E3779B1u) ^ (b * 0x85EBCA77u) ^ (seed * 0xC2B2AE3Du);
     h ^= h >> 15;
     h *= 0x27D4EB2Fu;
@@ -34,6 +36,7 @@ struct Stub {
     if (h % 5 == 0) return kNoRank;
     if (h % 61 == 1) return 0;
     if (h % 61 == 2) return 0xFFFEu;
+    if (h % 61 == 3) return 0xFFFDu;
     return (h >> 8) % (seed % 3 == 0 ? 7u : 0xFFFFu);  // (few distinct values: many ties)
   }
   uint32_t new_id(uint32_t v) const { return compact ? v : (v * 31u + 7u) % 0xFFFFu; }
@@ -156,7 +159,7 @@ uint32_t rnd() {
 }
 
 void fill_tokens(Model& md, uint32_t m, int variant) {
-  static const uint32_t special[4] = {0u, 0xFFFEu, 1u, 0x8000u};
+  static const uint32_t special[4] = {0u, 0xFFFEu, 0xFFFDu, 0x8000u};
   md.m = m;
   for (uint32_t k = 0; k < 16; k++) {
     uint32_t v = variant == 0 ? 100u + k : variant == 1 ? special[(k + m) & 3] : rnd() % 0xFFFFu;
@@ -166,10 +169,10 @@ void fill_tokens(Model& md, uint32_t m, int variant) {
 }
 
 void directed() {
-  static const uint32_t lows[3] = {0u, 5u, 0xFFFEu};
+  static const uint32_t lows[4] = {0u, 5u, 0xFFFDu, 0xFFFEu};
   for (uint32_t m = 9; m <= 16; m++)
     for (int variant = 0; variant < 3; variant++)
-      for (int mode = 0; mode < 4; mode++)
+      for (int mode = 0; mode < 5; mode++)
         for (uint32_t low : lows)
           for (int others = 0; others < 2; others++) {  // 0: the other pairs have no value; 1: higher values
             if (others == 1 && low == 0xFFFEu) continue;
@@ -206,7 +209,7 @@ void random_runs(int runs) {
     md.m = m;
     for (uint32_t k = 0; k < 16; k++) {
       const uint32_t v = (it & 1) ? rnd() % alpha : (k % alpha);
-      md.tk[k] = k < m ? (v == 0 ? 0u : v == 1 ? 0xFFFEu : v * 1000u) : kDead;
+      md.tk[k] = k < m ? (v == 0 ? 0u : v == 1 ? 0xFFFEu : v == 2 ? 0xFFFDu : v * 1000u) : kDead;
     }
     for (uint32_t k = 0; k < 16; k++) md.rk[k] = k + 1 < m ? st.value(md.tk[k], md.tk[k + 1]) : kNoRank;
     Packed pk;
@@ -231,7 +234,8 @@ void tier_runs(int runs) {  // m16::tier against the stepped model
     st.seed = rnd();
     Model md;
     md.m = 9 + rnd() % 8;
-    for (uint32_t k = 0; k < 16; k++) md.tk[k] = k < md.m ? 3u + rnd() % 4 : kDead;
+    const uint32_t hi = (it & 1) ? 0xFFFBu : 3u;  // tokens 3..6, or the four largest ids 0xFFFB..0xFFFE
+    for (uint32_t k = 0; k < 16; k++) md.tk[k] = k < md.m ? hi + rnd() % 4 : kDead;
     for (uint32_t k = 0; k < 16; k++) md.rk[k] = k + 1 < md.m ? st.value(md.tk[k], md.tk[k + 1]) : kNoRank;
     Packed pk;
     load(md, pk);

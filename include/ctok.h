@@ -104,6 +104,27 @@ int ctok_special_token(const ctok* tok, uint64_t i, char* buf, size_t cap, size_
 uint64_t ctok_num_piece_added_tokens(const ctok* tok);
 int ctok_piece_can_contain(const uint8_t* raw, size_t len);
 
+/* Diagnostics of the 16-bit id decisions (read-only; nothing depends on them).  Each field is 1, 0
+ * or -1 for "not known yet": the dev_* fields before the first call on `device` has built its
+ * tables, the last_* fields before the first encode call on it.
+ *   narrow:       every model-vocab id < 0xFFFF (the 32-bit-key pair tables, u16 token slots and
+ *                 u16 piece records; 0xFFFF is their sentinel)
+ *   compact:      merge-table values are the new ids (strictly increasing in rank), not ranks
+ *   short_packed: narrow, compact, no value whose lookup panics and every value < 0xFFFF: the
+ *                 packed u16-pair 16-slot tier of the 9..16-byte pass can run
+ *   ids16:        narrow, and every added token that can match inside a piece has an id < 0xFFFF:
+ *                 ids cross the link as 16-bit values in ctok_encode_batch
+ *   dev_narrow, dev_short_packed: the two as built into the device tables, after the environment
+ *                 switches read at that time (CTOK_FORCE_WIDE_SLOTS, CTOK_SHORT_PACKED)
+ *   last_rec16:   the last encode call on the device kept its piece records as u16
+ *   last_wire16:  the last ctok_encode_batch on the device sent its ids as 16-bit values */
+typedef struct ctok_table_props {
+  int narrow, compact, short_packed, ids16;
+  int dev_narrow, dev_short_packed;
+  int last_rec16, last_wire16;
+} ctok_table_props;
+int ctok_get_table_props(const ctok* tok, int device, ctok_table_props* out);
+
 /* Execution / measurement options for one encode call. */
 typedef struct ctok_exec {
   int device;       /* HIP device ordinal the work runs on                              */

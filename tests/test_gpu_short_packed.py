@@ -108,6 +108,10 @@ def test_short_tiers_vs_oracle(batch, tables, name, packed):
         tok = Tokenizer.from_str(js)
         ids, toff = tok.encode_packed(text, off, timing=True)
         st = tok.last_stats
+    # the tier that ran (Tokenizer.table_props): packed for the gpt2 table unless switched off
+    p = tok.table_props
+    assert p["short_packed"] == (name == "gpt2") and p["narrow"] == (name != "llama3")
+    assert p["dev_short_packed"] == (name == "gpt2" and packed is None)
     assert_same(ids, toff, ref_ids, ref_off)
     # the 9..16 B class did the work: 320 documents x at least 7 letter pieces of >= 9 bytes
     assert st["class_bytes"][1] > 20000 and st["class_ids"][1] > 0
@@ -122,5 +126,6 @@ def test_two_calls_same_output(batch, tables):
         tok = Tokenizer.from_str(js)
         a_ids, a_off = tok.encode_packed(text, off)
         b_ids, b_off = tok.encode_packed(text, off)
+    assert tok.table_props["dev_short_packed"]
     assert np.array_equal(a_ids, b_ids) and np.array_equal(a_off, b_off)
     assert_same(b_ids, b_off, ref_ids, ref_off)

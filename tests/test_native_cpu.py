@@ -280,3 +280,103 @@ def test_cp_range_classes_match_tables():
             assert n2[n1[cp >> 8] * 256 + (cp & 255)] == 0, hex(cp)
             ch = chr(cp)
             assert (1 if rl.match(ch) else 0 if rs.match(ch) else 2 if rn.match(ch) else 3) == want, hex(cp)
+
+
+@pytest.fixture(scope="module")
+def boundary_tables(llama3_path):
+    from tests import id16_cases
+    with open(llama3_path) as f:
+        base = json.load(f)
+    return {n: toys.truncated(base, n) for n in id16_cases.N_IDS}
+
+
+def _loaded_props(obj):
+    p = Tokenizer.from_str(json.dumps(obj)).table_props
+    # no device call has run: the device-side fields are unknown
+    assert [p[k] for k in ("dev_narrow", "dev_short_packed", "last_rec16", "last_wire16")] == [None] * 4
+    return {k: p[k] for k in ("narrow", "compact", "short_packed", "ids16")}
+
+
+@pytest.mark.parametrize("fixture", ["gpt2_path", "llama3_path", "multi_path"])
+def test_table_props_of_fixtures(fixture, request):
+    """The 16-bit id decisions of the loader (Tokenizer.table_props) against the rules it states,
+    restated on the JSON object (tests/id16_cases.expected_props): the committed fixtures."""
+    from tests import id16_cases
+    with open(request.getfixturevalue(fixture)) as f:
+        obj = json.load(f)
+    want = id16_cases.expected_props(obj)
+    assert want["narrow"] == (fixture != "llama3_path") and want["compact"]  # (what the suite relies on)
+    assert _loaded_props(obj) == want
+
+
+def test_table_props_at_the_16_bit_boundary(boundary_tables):
+    """Tables of 65,534 .. 65,537 ids: the largest id of a narrow table is 0xFFFE (0xFFFF is the
+    sentinel of the u16 slots, values and records), so the first two are narrow and packed, the
+    last two are neither."""
+    from tests import id16_cases
+    flip = boundary_tables[65535]
+    for n, obj in boundary_tables.items():
+        want = id16_cases.expected_props(obj)
+        assert want == {"narrow": n <= 65535, "compact": True, "short_packed": n <= 65535, "ids16": n <= 65535}
+        assert max(obj["model"]["vocab"].values()) == n - 1
+        assert _loaded_props(obj) == want, n
+
+
+def test_table_props_of_tables_without_the_packed_tier(boundary_tables):
+    """Rank-valued and panicking derivations of the 65,535-id table stay narrow without the packed
+    tier."""
+    from tests import id16_cases
+    flip = boundary_tables[65535]
+    derived = {
+        "shuffled": (toys.shuffled_merges(flip, seed=16), (True, False, False, True)),
+        "last_two_swapped": (toys.swapped_last_merges(flip), (True, False, False, True)),
+        "invalid": (toys.with_invalid_merges(flip, seed=0, n_bad=30), (True, True, False, True)),
+        "invalid_front": (toys.with_invalid_merge_in_front(flip), (True, True, False, True)),
+        # invalid merges after every valid one shift nothing: no panicking value
+        "invalid_tail": (toys.with_invalid_merges(flip, seed=4, n_bad=30, tail_only=True), (True, True, True, True)),
+        "shuffled_wide": (toys.shuffled_merges(boundary_tables[65536], seed=16), (False, False, False, False)),
+    }
+    for name, (obj, flags) in derived.items():
+        want = id16_cases.expected_props(obj)
+        assert tuple(want[k] for k in ("narrow", "compact", "short_packed", "ids16")) == flags, name
+        assert _loaded_props(obj) == want, name
+
+
+def test_table_props_with_added_tokens(boundary_tables):
+    """ids16: only the added tokens that can match inside a piece count, and 0xFFFE is the last
+    16-bit id."""
+    from tests import id16_cases
+    flip, small = boundary_tables[65535], boundary_tables[65534]
+    cases = [
+        (flip, id16_cases.ADDED_IDS, True, False),                       # 65,535 / 65,536 / 70,000
+        (flip, {"ing": 65535}, True, False),
+        (flip, {"ing": 65534, "ll": 0}, True, True),                     # (ids may repeat the vocab's)
+        (small, {"ing": 65534}, True, True),
+        (small, {"ing": 65534, "zz": 65535}, True, False),
+        (flip, {"<|endoftext|>": 70000, "[CLS]": 65535}, True, True),    # never inside a piece
+        (boundary_tables[65536], {"ing": 5}, False, False),              # a wide vocabulary: never ids16
+    ]
+    for base, added, narrow, ids16 in cases:
+        obj = id16_cases.with_added_ids(base, added)
+        tok = Tokenizer.from_str(json.dumps(obj))
+        in_piece = [i for c, i in added.items()
+                    if _native.lib.ctok_piece_can_contain(c.encode(), len(c.encode())) == 1]
+        assert tok.num_piece_added_tokens() == len(in_piece)
+        want = id16_cases.expected_props(obj, in_piece)
+        assert (want["narrow"], want["ids16"]) == (narrow, ids16), added
+        assert _loaded_props(obj) == want, added
+
+
+def test_boundary_corpus_reaches_every_length_class(boundary_tables):
+    """The precondition of tests/test_gpu_id16_boundary.py, on the C oracle alone: the boundary
+    words of the 65,535-id table put id 0xFFFE into a multi-token piece of every length class, and
+    an id of the top 64 into at least 100 of each."""
+    from datagen import corpus
+    from oracle import ref_c
+    from tests import id16_cases
+    obj = boundary_tables[65535]
+    docs = id16_cases.boundary_docs(obj)
+    assert len(docs) == 64 * 11 * 6
+    ids, off = ref_c.RefC(obj).encode_packed(*corpus.pack([d.encode() for d in docs]))
+    top, near = id16_cases.assert_reaches_every_class(docs, ids, off, 65535)
+    assert top == [6, 24, 12, 12, 12]  # (as measured when the corpus was designed: it has not drifted)

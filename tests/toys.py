@@ -66,6 +66,17 @@ def shuffled_merges(base_obj, seed):
     return derived(base_obj, m)
 
 
+def swapped_last_merges(base_obj):
+    """Same vocab, the last two merges in each other's place: every token still merges as before
+    when the two are independent, but the new ids no longer rise with the rank, so the table's
+    values are ranks (not compact)."""
+    def m(o):
+        ms = list(o["model"]["merges"])
+        ms[-1], ms[-2] = ms[-2], ms[-1]
+        o["model"]["merges"] = ms
+    return derived(base_obj, m)
+
+
 def with_invalid_merge_in_front(base_obj):
     """One merge whose parts are not in the vocab, in front: every valid merge's rank shifts by one
     (src/bpe.rs:60-69), so a merge's new id is the previous merge's and the last valid merge panics
@@ -86,6 +97,26 @@ def with_invalid_merges(base_obj, seed, n_bad=50, tail_only=False):
             ms.insert(pos, "zz%dq qq%dz" % (k, k))
         o["model"]["merges"] = ms
     return derived(base_obj, m)
+
+
+def truncated(base_obj, n_ids):
+    """The first n_ids ids of a table laid out as the llama3_128k fixture is: the byte chars are ids
+    0..255, merge r makes id 256 + r and both its parts have smaller ids, so the vocab entries with
+    id < n_ids and the first n_ids - 256 merges are a closed, rank-monotone, compact table whose
+    largest id is n_ids - 1 (the layout is asserted).  Added tokens are dropped; everything else
+    (pre-tokenizer, decoder, ...) is the base's.  For tables at the 16-bit id boundary."""
+    vocab = base_obj["model"]["vocab"]
+    merges = base_obj["model"]["merges"][:n_ids - 256]
+    assert 256 < n_ids <= len(vocab) and len(merges) == n_ids - 256
+    keep = {t: i for t, i in vocab.items() if i < n_ids}
+    assert len(keep) == n_ids
+    for r, m in enumerate(merges):
+        a, b = m.split(" ") if isinstance(m, str) else m
+        assert keep[a + b] == 256 + r and keep[a] < 256 + r and keep[b] < 256 + r, (r, m)
+    obj = {k: v for k, v in base_obj.items() if k not in ("model", "added_tokens")}
+    obj["added_tokens"] = []
+    obj["model"] = dict(base_obj["model"], vocab=keep, merges=list(merges))
+    return json.loads(json.dumps(obj))
 
 
 def eager_cascade():
