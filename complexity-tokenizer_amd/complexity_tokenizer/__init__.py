@@ -293,12 +293,16 @@ class Tokenizer:
         tokenizer selects -- the load-time properties (narrow, compact, short_packed, ids16) as
         bools, and for self.device the two built into its device tables after the environment
         switches (dev_narrow, dev_short_packed) and the last encode call's piece-record and wire
-        formats (last_rec16, last_wire16); those four are None until such a call has run."""
-        tp = _n.TableProps()
+        formats (last_rec16, last_wire16); those four are None until such a call has run.
+        dev_mid_packed (0, 1, 2: how the device tables run the 17..32-byte pass, CTOK_MID_PACKED) is
+        an int, None as the other dev_* entries."""
+        tp = _n.TableProps(dev_mid_packed=-1)
         rc = _n.lib.ctok_get_table_props(self._h, int(self.device), ctypes.byref(tp))
         if rc != _n.CTOK_OK:
             _raise(rc)
-        return {k: None if getattr(tp, k) < 0 else bool(getattr(tp, k)) for k, _ in tp._fields_}
+        d = {k: None if getattr(tp, k) < 0 else bool(getattr(tp, k)) for k, _ in tp._fields_}
+        d["dev_mid_packed"] = None if tp.dev_mid_packed < 0 else int(tp.dev_mid_packed)
+        return d
 
     # ------------------------------------------------------------------ encode
     def encode_packed(self, text: np.ndarray, off: np.ndarray, timing: bool = False):

@@ -116,7 +116,7 @@ class Tables(ctypes.Structure):  # include/ctok.h ctok_tables
 
 class TableProps(ctypes.Structure):  # include/ctok.h ctok_table_props
     _fields_ = [(k, ctypes.c_int) for k in ("narrow", "compact", "short_packed", "ids16", "dev_narrow",
-                                            "dev_short_packed", "last_rec16", "last_wire16")]
+                                            "dev_short_packed", "last_rec16", "last_wire16", "dev_mid_packed")]
 
 
 class TrainerConfig(ctypes.Structure):  # include/ctok_trainer.h

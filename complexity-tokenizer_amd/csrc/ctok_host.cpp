@@ -1500,6 +1500,15 @@ DeviceState* device_state(ctok* t, int device) {
     const char* pk = getenv("CTOK_SHORT_PACKED");
     tb.short_packed = (tb.narrow && t->short_packed && !(pk && atoi(pk) == 0)) ? 1 : 0;
   }
+  {  // CTOK_MID_PACKED: the 17..32 B pass of tables with the property (Tables::mid_packed; A/B arms, the
+     // tests run all three).  The third pass of k_bpe_short belongs to its packed instance: with
+     // CTOK_SHORT_PACKED=0, 2 is 1.
+    const char* mp = getenv("CTOK_MID_PACKED");
+    const int want = mp ? atoi(mp) : kMidPackedDefault;
+    uint32_t v = (tb.narrow && tb.compact && t->short_packed && want > 0) ? (want >= 2 ? 2u : 1u) : 0u;
+    if (v == 2 && !tb.short_packed) v = 1;
+    tb.mid_packed = v;
+  }
   tb.all_bytes = std::all_of(t->byte2id, t->byte2id + 256, [](int32_t v) { return v >= 0; }) ? 1 : 0;
   tb.dbg = getenv("CTOK_DBG_MODE") ? (uint32_t)atoi(getenv("CTOK_DBG_MODE")) : 0;
   DeviceState* r = ds.get();
@@ -1952,11 +1961,18 @@ uint64_t encode_device(ctok* t, DeviceState* ds, const uint8_t* d_text, const ui
   // disjoint); no fork event -- the report orders it after k_segment --, one join before the tail
   const char* ov_var = getenv("CTOK_OVERLAP");
   const int overlap = ov_var ? atoi(ov_var) : kOverlapDefault;
-  const bool mid_side = overlap >= 1 && seg_cnt[0] == 0;
+  // (k_bpe_short took the class as its third pass: the same decision from the same counter, mid_folded)
+  const bool folded = nt && mid_folded(tb, seg_cnt[0]);
+  const bool mid_side = !folded && overlap >= 1 && seg_cnt[0] == 0;
   ds->last_mid_side = mid_side;
-  STEP("bpe_mid", launch_bpe_class(w, tb, 2, mid_side ? ds->side : s, lx(8, 10)));
-  if (c3_sparse) STEP("bpe_c3_sparse", launch_c3_sparse(w, tb, c3n, s, lx(-1, 9)));
-  else STEP("bpe_c3", launch_bpe_class(w, tb, 4, s, lx(-1, 9)));
+  if (!folded) STEP("bpe_mid", launch_bpe_class(w, tb, 2, mid_side ? ds->side : s, lx(8, 10)));
+  // With the class folded the side stream is idle again: the 33..64 B pass -- register or sparse --
+  // goes there and takes the CUs k_bpe_short's workgroups free as they end, instead of starting
+  // after the last of them (C4: 0.05 ms, profiles/mid32_packed/ab_summary.txt; CTOK_OVERLAP=0: main)
+  const bool c3_side = folded && overlap >= 1 && (c3n != 0 || seg_cnt[kCtrAnyC3] != 0);
+  hipStream_t c3s = c3_side ? ds->side : s;
+  if (c3_sparse) STEP("bpe_c3_sparse", launch_c3_sparse(w, tb, c3n, c3s, lx(-1, 9)));
+  else STEP("bpe_c3", launch_bpe_class(w, tb, 4, c3s, lx(-1, 9)));
   if (!spec_fail1 && n_long) {
     for (;;) {  // the long pieces' totals (launch_long_prep above)
       const hipError_t e = hipEventQuery(ds->ev_tot);
@@ -1970,7 +1986,7 @@ uint64_t encode_device(ctok* t, DeviceState* ds, const uint8_t* d_text, const ui
     w.lw = ds->lw.p;
     STEP("bpe_long", launch_bpe_long(w, tb, ds->side, n_long, seg_cnt[kCtrAnyC3] != 0 && !c3_sparse, any_gmem));
   }
-  if (n_long || mid_side) {
+  if (n_long || mid_side || c3_side) {
     HIPTRY(hipEventRecord(ds->ev_join, ds->side));
     HIPTRY(hipStreamWaitEvent(s, ds->ev_join, 0));
   }
@@ -1996,10 +2012,11 @@ uint64_t encode_device(ctok* t, DeviceState* ds, const uint8_t* d_text, const ui
     lap[2] = laps.add(e[1], e[2]);  // <= 16 B pass (from k_segment's end)
     // class 2; on the side stream its events span the wait for k_bpe_short's CUs, so the time it
     // adds after k_bpe_short's end is reported
-    lap[3] = !passes ? -1 : mid_side ? laps.add(e[2], e[10]) : laps.add(e[8], e[10]);
+    // (nothing when k_bpe_short took it: lap[2] then contains the class)
+    lap[3] = !passes || folded ? -1 : mid_side ? laps.add(e[2], e[10]) : laps.add(e[8], e[10]);
     lap[4] = passes ? laps.add(e[2], e[9]) : -1;  // class 3 (register or sparse pass; after k_bpe_short)
     lap[5] = laps.add(e[1], e[2]);  // k_segment's end to the merge passes' ends
-    lap[6] = passes ? laps.add(e[1], e[10]) : -1;
+    lap[6] = passes && !folded ? laps.add(e[1], e[10]) : -1;
     lap[7] = passes ? laps.add(e[1], e[9]) : -1;
     lap[8] = laps.add(e[1], e[dropped_pass ? 5 : 3]);  // ... to the tail's start
     lap[9] = laps.add(e[3], e[6]);  // tile scan + emit
@@ -2745,7 +2762,7 @@ uint64_t ctok_num_piece_added_tokens(const ctok* t) { return t ? t->at_id.size()
 int ctok_get_table_props(const ctok* tc, int device, ctok_table_props* out) {
   if (!tc || !out) return fail(CTOK_E_ARG, "null argument");
   ctok* t = const_cast<ctok*>(tc);
-  *out = ctok_table_props{t->narrow, t->compact, t->short_packed, t->ids16, -1, -1, -1, -1};
+  *out = ctok_table_props{t->narrow, t->compact, t->short_packed, t->ids16, -1, -1, -1, -1, -1};
   std::lock_guard<std::mutex> lk(t->dev_mu);
   auto it = t->devs.find(device);
   if (it != t->devs.end()) {
@@ -2754,6 +2771,7 @@ int ctok_get_table_props(const ctok* tc, int device, ctok_table_props* out) {
     out->dev_short_packed = (int)ds.t.short_packed;
     out->last_rec16 = ds.last_rec16;
     out->last_wire16 = ds.last_wire16;
+    out->dev_mid_packed = (int)ds.t.mid_packed;
   }
   return CTOK_OK;
 }

@@ -51,7 +51,8 @@ constexpr int kCtrC3Count = 22;    // counters[22] of the report: class-3 pieces
 constexpr int kCtrC3Take = 23;     // counters[23]: next piece of the sparse class-3 pass
 constexpr uint32_t kC3SparseDefault = 65536;  // the most pieces the sparse class-3 path takes by default (ctok_host.cpp)
 constexpr uint32_t kWgRecWords = 4 * 1024 * 4;  // Work::wgrec: 4 kernels x 1024 workgroups x 4 words
-constexpr int kOverlapDefault = 1;             // merge passes on the side stream without long pieces (CTOK_OVERLAP)
+constexpr int kMidPackedDefault = 2;           // the 17..32 B pass of short_packed tables (CTOK_MID_PACKED, Tables::mid_packed)
+constexpr int kOverlapDefault = 1;            // merge passes on the side stream without long pieces (CTOK_OVERLAP)
 constexpr int kCtrSink = 31;       // counters[31]: panic bits of lookups whose pairs need not exist (discarded)
 constexpr int kCtrOverflow = 25;   // counters[25] != 0: a list outgrew its lean capacity (the host reruns the call safe)
 constexpr int kCtrLongIds = 26;    // counters[26]: long-piece id slots reserved (k_long_len: a piece's bytes)
@@ -223,9 +224,20 @@ struct Tables {            // device pointers, owned by the host runtime
   uint32_t narrow;          // 1: every vocab id < 2^16 (the merge passes keep the last tier's tokens as u16 in LDS)
   uint32_t short_packed;    // 1 (narrow and compact only): every value of pair0, merge16 and the narrow LDS image is
                             // < 0xFFFF and none panics, so k_bpe_short's 16-slot tier keeps values as u16 pairs (merge16_hd.h)
+  uint32_t mid_packed;      // the 17..32 B pass of such tables (CTOK_MID_PACKED): 0 the u32 register tiers in k_bpe_mid<2>,
+                            // 1 the packed 32-slot tier (merge32_hd.h) in k_bpe_mid<2>, 2 the packed tier as the third
+                            // pass of k_bpe_short when the call has no long piece (mid_folded), else as 1
   uint32_t dbg;             // debug mode (CTOK_DBG_MODE), 0 in production
   uint32_t all_bytes;       // 1: every byte's char is in the vocab (no piece can have a dropped byte)
 };
+
+// Does k_bpe_short take the 17..32 B class as its third pass?  The one decision of both sides, from
+// one value: long_pieces is counters[0], final once k_segment has completed -- the kernel reads it
+// on the device, the host in the report (the same word, copied by the kernel's first wave).  The
+// host launches k_bpe_mid<2> exactly when this is false.
+__host__ __device__ inline bool mid_folded(const Tables& t, uint32_t long_pieces) {
+  return t.mid_packed == 2 && t.short_packed && t.n_at == 0 && long_pieces == 0;
+}
 
 struct Work {              // device pointers, sized by the host for one call
   const uint8_t* text;     // (normalised) text

@@ -31,6 +31,7 @@
 
 #include "ctok_internal.h"
 #include "merge16_hd.h"
+#include "merge32_hd.h"
 #include "seg_lane.h"
 
 namespace ctok_dev {
@@ -1498,8 +1499,16 @@ __device__ __forceinline__ void store_packed_ids(const uint32_t (&T)[8], uint32_
     store_packed_ids<K0 + 1, K1>(T, m, out);
   }
 }
+template <int K0, int K1>
+__device__ __forceinline__ void store_packed_ids(const uint32_t (&T)[16], uint32_t m, uint32_t* out) {
+  if constexpr (K0 < K1) {
+    if ((uint32_t)K0 < m) out[K0] = m32::half<K0>(T);
+    store_packed_ids<K0 + 1, K1>(T, m, out);
+  }
+}
 
 // Workgroup-shared scratch of a merge pass.
+// (KT: the most tiles per chunk of the passes that share it)
 template <uint32_t SORTCAP, int KT = 64>
 struct PassLds {
   uint32_t pre[KT + 1], tsum[KT], tbase[KT], stat[2], bcnt[4], bfill[4], chunk, take, next;
@@ -1515,16 +1524,20 @@ struct PassLds {
 // work, so a workgroup that finds only empty lists never reads the 32..96 KiB image (`loaded`
 // is shared by the passes of one kernel).
 // L8: the <= 8-token tier runs in LDS (merge_lds8, narrow vocabularies; s_key / s_tok its state).
-// PK (N = 16, L8): the 16-slot tier keeps tokens and values as u16 pairs (merge16_hd.h; tables
-// whose values all fit, Tables::short_packed).
+// PK (N = 16 or 32, L8): the 16-slot tier, and at N = 32 the 32-slot tier before it, keep tokens
+// and values as u16 pairs (merge16_hd.h, merge32_hd.h; tables whose values all fit,
+// Tables::short_packed).
+// LA: the pipeline loads the next piece's text one block ahead (N / 4 + 1 registers held through the
+// merges); without it only the list entry is looked ahead and a piece loads its own text.
 template <int N, bool COMPACT, bool HOT, uint32_t NT, uint32_t SORTCAP, bool L8 = false, int KT = 64, bool PK = false,
-          typename Load>
+          bool LA = true, typename Load, int SKT>
 __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const PairLds& P, const int32_t* s_b2id,
-                                           PassLds<SORTCAP, KT>& S, bool& loaded, Load&& load,
+                                           PassLds<SORTCAP, SKT>& S, bool& loaded, Load&& load,
                                            lds_u32* s_key = nullptr, lds_u16* s_tok = nullptr) {
   using LC = LdsClass<N>;
   constexpr int K = KT;
   static_assert(KT <= (int)NT, "a thread per chunk tile");
+  static_assert(KT <= SKT, "the shared scratch holds the pass's chunk");
   const uint32_t tid = threadIdx.x;
   uint32_t* err = &w.counters[2];
   const uint32_t* list = class_list<N>(w);
@@ -1606,16 +1619,18 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
         const uint32_t o = ent_ord(e);
         const uint32_t n = ent_len(e);
         if constexpr (PK) {
-          static_assert(N == 16 && L8 && COMPACT, "the packed tier is the 9..16 B pass's, ahead of merge_lds8, on compact tables");
+          static_assert((N == 16 || N == 32) && L8 && COMPACT,
+                        "the packed tiers are the 9..16 B and 17..32 B passes', ahead of merge_lds8, on compact tables");
           // packed tokens straight from the byte -> id table, packed values from the byte-pair
           // table (no entry of it panics and every value fits 16 bits: Tables::short_packed;
           // kNoRank's low half is m16::kNone)
-          uint32_t T[8], R[8], bytes[N];
+          constexpr int ND = N / 2;
+          uint32_t T[ND], R[ND], bytes[N];
           bool missing = false;
 #pragma unroll
           for (int k = 0; k < N; k++) bytes[k] = byte_of(wv[k >> 2], k);
 #pragma unroll
-          for (int d = 0; d < 8; d++) {
+          for (int d = 0; d < ND; d++) {
             const int32_t i0 = s_b2id[bytes[2 * d]], i1 = s_b2id[bytes[2 * d + 1]];
             missing |= (((uint32_t)(2 * d) < n) & (i0 < 0)) | (((uint32_t)(2 * d + 1) < n) & (i1 < 0));
             T[d] = m16::pack2((uint32_t)i0, (uint32_t)i1);
@@ -1637,25 +1652,43 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
 #pragma unroll
             for (int k = 0; k < N - 1; k++) v[k] = (uint32_t)k + 1 < n ? v[k] : kNoRank;
 #pragma unroll
-            for (int d = 0; d < 8; d++) R[d] = m16::pack2(v[2 * d], v[2 * d + 1]);
+            for (int d = 0; d < ND; d++) R[d] = m16::pack2(v[2 * d], v[2 * d + 1]);
           }
           uint32_t m = n;
           Lookup16<HOT> lk{t, P, err};
-          const bool more = m16::tier(T, R, m, 8u, lk);
-          hook();
           uint32_t pos = 0;
           auto out_of = [&](uint32_t mm) {
             pos = atomicAdd(&S.tsum[kt], mm);
             return w.scratch + (size_t)tile * kTileSlots + pos;
           };
-          if (more) {
-            lds8_store_packed<0, 8, NT>(T, R, s_key, s_tok);
-            m = merge_lds8_run<COMPACT, HOT, NT>(t, P, m, s_key, s_tok, err, out_of);
+          if constexpr (N == 32) {
+            // 32 slots down to <= 16 tokens, then the 16-slot tier on the low 8 + 8 dwords
+            bool more = m32::tier(T, R, m, 16u, lk);
+            uint32_t T8[8], R8[8];
+            m32::low_half(T, T8);
+            m32::low_half(R, R8);
+            if (more) more = m16::tier(T8, R8, m, 8u, lk);
+            hook();
+            if (more) {
+              lds8_store_packed<0, 8, NT>(T8, R8, s_key, s_tok);
+              m = merge_lds8_run<COMPACT, HOT, NT>(t, P, m, s_key, s_tok, err, out_of);
+            } else if (m > 16) {
+              store_packed_ids<0, N>(T, m, out_of(m));
+            } else {
+              store_packed_ids<0, 16>(T8, m, out_of(m));
+            }
           } else {
-            store_packed_ids<0, N>(T, m, out_of(m));
+            const bool more = m16::tier(T, R, m, 8u, lk);
+            hook();
+            if (more) {
+              lds8_store_packed<0, 8, NT>(T, R, s_key, s_tok);
+              m = merge_lds8_run<COMPACT, HOT, NT>(t, P, m, s_key, s_tok, err, out_of);
+            } else {
+              store_packed_ids<0, N>(T, m, out_of(m));
+            }
           }
           CTOK_CHECK_REC(m >= 1 && m <= n && pos + m <= (uint32_t)kTileSlots && o < (uint32_t)kTileSlots,
-                         "[ctok check] packed class pass tile %u: record m=%u n=%u pos=%u ordinal=%u\n", tile, m, n, pos, o);
+                         "[ctok check] packed class pass N=%d tile %u: record m=%u n=%u pos=%u ordinal=%u\n", N, tile, m, n, pos, o);
           w.mrec[(size_t)tile * kTileSlots + o] = rec_short(m, pos);
           st_bytes += n;
           st_ids += m;
@@ -1769,7 +1802,8 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
       };
       auto hook = [&]() {
         static_assert(kPw <= 8, "hook operands");
-        if constexpr (kPw == 2) asm volatile("" ::"v"(d0[0]), "v"(d0[1]), "v"(d0[2]), "v"(e1));
+        if constexpr (!LA) asm volatile("" ::"v"(e1));
+        else if constexpr (kPw == 2) asm volatile("" ::"v"(d0[0]), "v"(d0[1]), "v"(d0[2]), "v"(e1));
         else if constexpr (kPw == 4)
           asm volatile("" ::"v"(d0[0]), "v"(d0[1]), "v"(d0[2]), "v"(d0[3]), "v"(d0[4]), "v"(e1));
         else
@@ -1778,27 +1812,45 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
       };
       uint32_t b0 = take();
       uint32_t b1 = b0 < E ? take() : E;
-      if (b0 + lane < E) {
-        e0 = entry(b0 + lane, kt0);
-        issue_words(start_of(e0, kt0));
-      }
-      if (b1 + lane < E) e1 = entry(b1 + lane, kt1);
-      hook();
-      while (b0 < E) {  // wave-uniform
-        const uint32_t i = b0 + lane;
-        const uint32_t b2 = b1 < E ? take() : E;
-        const uint32_t e = e0, kt = kt0;
-        uint32_t wv[kPw];
+      if constexpr (LA) {
+        if (b0 + lane < E) {
+          e0 = entry(b0 + lane, kt0);
+          issue_words(start_of(e0, kt0));
+        }
+        if (b1 + lane < E) e1 = entry(b1 + lane, kt1);
+        hook();
+        while (b0 < E) {  // wave-uniform
+          const uint32_t i = b0 + lane;
+          const uint32_t b2 = b1 < E ? take() : E;
+          const uint32_t e = e0, kt = kt0;
+          uint32_t wv[kPw];
 #pragma unroll
-        for (int k = 0; k < kPw; k++) wv[k] = __builtin_amdgcn_alignbyte(d0[k + 1], d0[k], sh0);
-        e0 = e1;
-        kt0 = kt1;
-        if (b1 + lane < E) issue_words(start_of(e0, kt0));
-        if (b2 + lane < E) e1 = entry(b2 + lane, kt1);
-        b0 = b1;
-        b1 = b2;
-        if (i < E) body(e, kt, wv, hook);
-        else hook();
+          for (int k = 0; k < kPw; k++) wv[k] = __builtin_amdgcn_alignbyte(d0[k + 1], d0[k], sh0);
+          e0 = e1;
+          kt0 = kt1;
+          if (b1 + lane < E) issue_words(start_of(e0, kt0));
+          if (b2 + lane < E) e1 = entry(b2 + lane, kt1);
+          b0 = b1;
+          b1 = b2;
+          if (i < E) body(e, kt, wv, hook);
+          else hook();
+        }
+      } else {
+        // one stage: the list entry one block ahead (e1), the piece's own text loaded at its turn
+        if (b0 + lane < E) e1 = entry(b0 + lane, kt1);
+        while (b0 < E) {  // wave-uniform
+          const uint32_t i = b0 + lane;
+          const uint32_t b2 = b1 < E ? take() : E;
+          const bool live = i < E;
+          const uint32_t e = live ? e1 : 0u, kt = live ? kt1 : 0u;  // (idle lanes read the chunk's first bytes)
+          uint32_t wv[kPw];
+          load_words<kPw>(w.text, start_of(e, kt), w.n_bytes, wv);
+          if (b1 + lane < E) e1 = entry(b1 + lane, kt1);
+          b0 = b1;
+          b1 = b2;
+          if (live) body(e, kt, wv, hook);
+          else hook();
+        }
       }
     }
     tile_share_flush<K>(w, c0, tb1, S.tsum, S.tbase, LC::cls);
@@ -1855,15 +1907,27 @@ template <bool NARROW> struct ShortCfg {
 constexpr int kShortKT = 64;
 
 // PK16 (narrow compact tables with Tables::short_packed): the 9..16 B pass's 16-slot tier on u16 pairs.
-template <bool COMPACT, bool NARROW, bool PK16 = false>
+// PK32 (Tables::mid_packed == 2): the instance can also take the 17..32 B class as a third pass
+// on the packed 32-slot tier (passes bit 2), in the same workgroups with the image, the byte -> id
+// table and merge_lds8's state already in LDS.  It does so when the call has no long piece -- the
+// situation in which the host would otherwise put k_bpe_mid<2> on the idle side stream -- and it
+// reads that from the long-piece counter, final since k_segment completed; the host reads the same
+// counter in the report and launches k_bpe_mid<2> only when this kernel left the class alone
+// (mid_folded).  The class is sparse, so the pass takes k_bpe_mid's chunks of up to kMidKT tiles:
+// the shared scratch grows by 2.3 KB, taken from the sort buffer (kFoldSortCut entries of u16).
+constexpr int kMidKT = 256;
+constexpr uint32_t kFoldSortCut = 3 * (kMidKT - kShortKT) * 4 / 2;
+template <bool COMPACT, bool NARROW, bool PK16 = false, bool PK32 = false>
 __global__ __launch_bounds__(1024) void k_bpe_short(Work w, Tables t, uint32_t passes) {
   static_assert((NARROW && COMPACT) || !PK16, "the packed tier needs the narrow tables and compact values");
+  static_assert(PK16 || !PK32, "the third pass is the packed instance's");
   if (w.report && blockIdx.x == 0 && threadIdx.x < 64) write_report(w);  // (k_report's work: see there)
   if (spec_failed(w)) return;
   constexpr uint32_t NT = ShortCfg<NARROW>::NT;
+  constexpr uint32_t SORTCAP = ShortCfg<NARROW>::SORTCAP - (PK32 ? kFoldSortCut : 0u);
   extern __shared__ __attribute__((aligned(16))) uint4 s_img[];
   __shared__ int32_t s_b2id[256];
-  __shared__ PassLds<ShortCfg<NARROW>::SORTCAP, kShortKT> S;
+  __shared__ PassLds<SORTCAP, PK32 ? kMidKT : kShortKT> S;
   __shared__ uint32_t s_key[NARROW ? 8 * NT : 1];
   __shared__ uint16_t s_tok[NARROW ? 8 * NT : 1];
   const uint32_t tid = threadIdx.x;
@@ -1880,9 +1944,21 @@ __global__ __launch_bounds__(1024) void k_bpe_short(Work w, Tables t, uint32_t p
   // passes: bit 0 the <= 8 B class, bit 1 the 9..16 B class (both, except in the timing A/B
   // CTOK_DBG_MODE=30, which launches them as two kernels to time them apart)
   if (passes & 1u)
-    class_pass<8, COMPACT, true, NT, ShortCfg<NARROW>::SORTCAP, NARROW, kShortKT>(w, t, P, s_b2id, S, loaded, load, sk, st);
+    class_pass<8, COMPACT, true, NT, SORTCAP, NARROW, kShortKT>(w, t, P, s_b2id, S, loaded, load, sk, st);
   if (passes & 2u)
-    class_pass<16, COMPACT, true, NT, ShortCfg<NARROW>::SORTCAP, NARROW, kShortKT, PK16>(w, t, P, s_b2id, S, loaded, load, sk, st);
+    class_pass<16, COMPACT, true, NT, SORTCAP, NARROW, kShortKT, PK16>(w, t, P, s_b2id, S, loaded, load, sk, st);
+  if constexpr (PK32) {
+    if (passes & 4u) {  // (kernel argument: uniform)
+      // one read for the workgroup, handed round through LDS: every thread takes the same branch,
+      // so all 1024 reach class_pass's barriers or none does.  (S.next is free here: the passes
+      // above end with a barrier, and class_pass writes it only after its first one.)
+      if (tid == 0) S.next = (mid_folded(t, w.counters[0]) && w.counters[kCtrAnyMid] != 0) ? 1u : 0u;
+      __syncthreads();
+      const uint32_t fold = S.next;
+      if (fold)
+        class_pass<32, COMPACT, true, NT, SORTCAP, NARROW, kMidKT, true, false>(w, t, P, s_b2id, S, loaded, load, sk, st);
+    }
+  }
   WgRec::end(w.wgrec, 0, loaded ? 1u : 0u);
 }
 
@@ -2038,10 +2114,12 @@ __global__ __launch_bounds__(64 * kSparseWaves) void k_bpe_sparse(Work w, Tables
 // 152 KiB of LDS) when the call has no long pieces -- on C4 0.60 -> 0.55 ms --, else at 512: with
 // long pieces the side stream's tiers share the CUs, and 768 made C5 slower (+0.12 ms,
 // profiles/r05/v17_ab_mid768_c4_c5.txt).
-template <int CLS> struct MidCfg { static constexpr int KT = 256; };
+template <int CLS> struct MidCfg { static constexpr int KT = kMidKT; };
 
-template <bool COMPACT, int CLS, bool NARROW, uint32_t NT = 512>
+// PK (CLS = 2, Tables::mid_packed): the 32- and 16-slot tiers on u16 pairs (merge32_hd.h).
+template <bool COMPACT, int CLS, bool NARROW, uint32_t NT = 512, bool PK = false>
 __global__ __launch_bounds__(NT) void k_bpe_mid(Work w, Tables t) {
+  static_assert(!PK || (CLS == 2 && NARROW && COMPACT), "the packed tiers need the narrow tables and compact values");
   if (spec_failed(w)) return;
   constexpr int KT = MidCfg<CLS>::KT;
   extern __shared__ __attribute__((aligned(16))) uint4 s_img[];
@@ -2072,8 +2150,8 @@ __global__ __launch_bounds__(NT) void k_bpe_mid(Work w, Tables t) {
   for (uint32_t i = tid; i < 256; i += NT) s_b2id[i] = t.byte2id[i];
   bool loaded = true;
   const PairLds P{(const lds_u64*)s_img, (const lds_u32*)(s_img + kHotBuckets)};
-  class_pass<CLS == 2 ? 32 : 64, COMPACT, true, NT, kSortCap, NARROW, KT>(w, t, P, s_b2id, S, loaded, [] {},
-                                                                         (lds_u32*)s_key, (lds_u16*)s_tok);
+  class_pass<CLS == 2 ? 32 : 64, COMPACT, true, NT, kSortCap, NARROW, KT, PK>(w, t, P, s_b2id, S, loaded, [] {},
+                                                                             (lds_u32*)s_key, (lds_u16*)s_tok);
   if constexpr (CLS == 2) WgRec::end(w.wgrec, 1, 1);
 }
 
@@ -2095,46 +2173,51 @@ static hipError_t lds_attr_once(LdsAttr& a, const void* fn, size_t bytes) {
   return hipSuccess;
 }
 
-template <bool C, int CLS, bool NW>
+template <bool C, int CLS, bool NW, bool PK = false>
 static hipError_t launch_mid_t(const Work& w, const Tables& t, hipStream_t s, const Lx& x) {
   static LdsAttr attr;
-  HIPCHK(lds_attr_once(attr, (const void*)k_bpe_mid<C, CLS, NW>, kLdsImageBytes));
+  HIPCHK(lds_attr_once(attr, (const void*)k_bpe_mid<C, CLS, NW, 512, PK>, kLdsImageBytes));
   if (!w.n_tiles) return hipSuccess;
   const uint32_t grid = min((w.n_tiles + w.unit - 1) / w.unit, w.n_cus);
   if constexpr (CLS == 2) {
     if (w.mid_wide) {
       static LdsAttr attr768;
-      HIPCHK(lds_attr_once(attr768, (const void*)k_bpe_mid<C, CLS, NW, 768>, kLdsImageBytes));
-      launch_lx(x, k_bpe_mid<C, CLS, NW, 768>, grid, 768, kLdsImageBytes, s, w, t);
+      HIPCHK(lds_attr_once(attr768, (const void*)k_bpe_mid<C, CLS, NW, 768, PK>, kLdsImageBytes));
+      launch_lx(x, k_bpe_mid<C, CLS, NW, 768, PK>, grid, 768, kLdsImageBytes, s, w, t);
       return hipGetLastError();
     }
   }
-  launch_lx(x, k_bpe_mid<C, CLS, NW>, grid, 512, kLdsImageBytes, s, w, t);
+  launch_lx(x, k_bpe_mid<C, CLS, NW, 512, PK>, grid, 512, kLdsImageBytes, s, w, t);
   return hipGetLastError();
 }
 template <bool C, int CLS>
 static hipError_t launch_mid(const Work& w, const Tables& t, hipStream_t s, const Lx& x = {}) {
+  if constexpr (C && CLS == 2) {
+    if (t.narrow && t.mid_packed) return launch_mid_t<true, 2, true, true>(w, t, s, x);
+  }
   return t.narrow ? launch_mid_t<C, CLS, true>(w, t, s, x) : launch_mid_t<C, CLS, false>(w, t, s, x);
 }
 
-template <bool C, bool NW, bool PK = false>
+template <bool C, bool NW, bool PK = false, bool PK32 = false>
 static hipError_t launch_short_t(const Work& w, const Tables& t, hipStream_t s, const Lx& x) {
   static LdsAttr attr;
-  HIPCHK(lds_attr_once(attr, (const void*)k_bpe_short<C, NW, PK>, kLdsImageBytes));
+  HIPCHK(lds_attr_once(attr, (const void*)k_bpe_short<C, NW, PK, PK32>, kLdsImageBytes));
   if (!w.n_tiles) return hipSuccess;
   // (Work::short_wgs: fewer workgroups than CUs leave CUs to the side stream's passes from the start)
   const uint32_t grid = min((w.n_tiles + w.unit - 1) / w.unit, w.short_wgs ? min(w.short_wgs, w.n_cus) : w.n_cus);
   if (t.dbg == 30) {
-    k_bpe_short<C, NW, PK><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 1u);
-    k_bpe_short<C, NW, PK><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 2u);
+    k_bpe_short<C, NW, PK, PK32><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 1u);
+    k_bpe_short<C, NW, PK, PK32><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 2u);
+    if (PK32) k_bpe_short<C, NW, PK, PK32><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 4u);
   } else {
-    launch_lx(x, k_bpe_short<C, NW, PK>, grid, ShortCfg<NW>::NT, kLdsImageBytes, s, w, t, 3u);
+    launch_lx(x, k_bpe_short<C, NW, PK, PK32>, grid, ShortCfg<NW>::NT, kLdsImageBytes, s, w, t, PK32 ? 7u : 3u);
   }
   return hipGetLastError();
 }
 template <bool C>
 static hipError_t launch_short(const Work& w, const Tables& t, hipStream_t s, const Lx& x) {
   if constexpr (C) {
+    if (t.narrow && t.short_packed && t.mid_packed == 2) return launch_short_t<true, true, true, true>(w, t, s, x);
     if (t.narrow && t.short_packed) return launch_short_t<true, true, true>(w, t, s, x);
   }
   return t.narrow ? launch_short_t<C, true>(w, t, s, x) : launch_short_t<C, false>(w, t, s, x);

@@ -117,11 +117,17 @@ int ctok_piece_can_contain(const uint8_t* raw, size_t len);
  *   dev_narrow, dev_short_packed: the two as built into the device tables, after the environment
  *                 switches read at that time (CTOK_FORCE_WIDE_SLOTS, CTOK_SHORT_PACKED)
  *   last_rec16:   the last encode call on the device kept its piece records as u16
- *   last_wire16:  the last ctok_encode_batch on the device sent its ids as 16-bit values */
+ *   last_wire16:  the last ctok_encode_batch on the device sent its ids as 16-bit values
+ *   dev_mid_packed: 0, 1 or 2 (-1 as the other dev_* fields): how the device tables run the
+ *                 17..32-byte pass, after CTOK_MID_PACKED -- 0 on u32 register slots, 1 on the packed
+ *                 u16-pair 32-slot tier in its own kernel, 2 on that tier as the third pass of the
+ *                 <= 16-byte kernel when a call has no long piece (else as 1); 0 on every table
+ *                 without short_packed */
 typedef struct ctok_table_props {
   int narrow, compact, short_packed, ids16;
   int dev_narrow, dev_short_packed;
   int last_rec16, last_wire16;
+  int dev_mid_packed;
 } ctok_table_props;
 int ctok_get_table_props(const ctok* tok, int device, ctok_table_props* out);
 
