@@ -1194,7 +1194,7 @@ void load_root(ctok* t, const ctj::Value& root) {
       const uint32_t r = it->second;
       t->pair0[a * 256 + b] = t->compact ? (r < valid_new.size() ? valid_new[r] : kPanicVal) : r;
     }
-  // The packed 16-slot tier of k_bpe_short (merge16_hd.h) keeps table values as u16 with 0xFFFF
+  // The packed 16-slot tier of k_bpe_short (merge_packed_hd.h) keeps table values as u16 with 0xFFFF
   // for "none": every value it can see -- the byte-pair table, the narrow global table, the narrow
   // hot table -- must be below 0xFFFF, and none may be one whose lookup panics (the tier does not
   // check for those).  Compact tables (value = new id) of a narrow vocabulary without panicking

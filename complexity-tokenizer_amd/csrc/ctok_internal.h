@@ -223,9 +223,9 @@ struct Tables {            // device pointers, owned by the host runtime
   uint32_t compact;         // 1: entry values are new ids (strictly increasing in rank), else ranks
   uint32_t narrow;          // 1: every vocab id < 2^16 (the merge passes keep the last tier's tokens as u16 in LDS)
   uint32_t short_packed;    // 1 (narrow and compact only): every value of pair0, merge16 and the narrow LDS image is
-                            // < 0xFFFF and none panics, so k_bpe_short's 16-slot tier keeps values as u16 pairs (merge16_hd.h)
+                            // < 0xFFFF and none panics, so k_bpe_short's 16-slot tier keeps values as u16 pairs (merge_packed_hd.h)
   uint32_t mid_packed;      // the 17..32 B pass of such tables (CTOK_MID_PACKED): 0 the u32 register tiers in k_bpe_mid<2>,
-                            // 1 the packed 32-slot tier (merge32_hd.h) in k_bpe_mid<2>, 2 the packed tier as the third
+                            // 1 the packed 32-slot tier (merge_packed_hd.h) in k_bpe_mid<2>, 2 the packed tier as the third
                             // pass of k_bpe_short when the call has no long piece (mid_folded), else as 1
   uint32_t dbg;             // debug mode (CTOK_DBG_MODE), 0 in production
   uint32_t all_bytes;       // 1: every byte's char is in the vocab (no piece can have a dropped byte)

@@ -30,8 +30,7 @@
 #include <type_traits>
 
 #include "ctok_internal.h"
-#include "merge16_hd.h"
-#include "merge32_hd.h"
+#include "merge_packed_hd.h"
 #include "seg_lane.h"
 
 namespace ctok_dev {
@@ -1459,7 +1458,7 @@ __device__ __forceinline__ uint32_t merge_lds8(const Tables& t, const PairLds& P
   return merge_lds8_run<COMPACT, HOT, NT>(t, P, m, s_key, s_tok, err, out_of);
 }
 
-// The packed 16-slot tier (merge16_hd.h) over the pass's tables: the two lookups of a step as
+// The packed tiers (merge_packed_hd.h) over the pass's tables: the two lookups of a step as
 // Probe<true, HOT>, their loads in flight while the step moves its slots.  Compact tables only
 // (Tables::short_packed): a value is the merged token's id.
 template <bool HOT>
@@ -1476,7 +1475,7 @@ struct Lookup16 {
     pl.start(t, P, L, nid, hl);
     pr.start(t, P, nid, R, hr);
   }
-  // (kNoRank's low 16 bits are m16::kNone; every other value is < 0xFFFF: Tables::short_packed)
+  // (kNoRank's low 16 bits are mpk::kNone; every other value is < 0xFFFF: Tables::short_packed)
   __device__ __forceinline__ void finish(uint32_t& rl, uint32_t& rr) {
     rl = (has_l ? pl.finish(t, err) : kNoRank) & 0xFFFFu;
     rr = (has_r ? pr.finish(t, err) : kNoRank) & 0xFFFFu;
@@ -1487,24 +1486,27 @@ template <int K0, int K1, uint32_t NT>
 __device__ __forceinline__ void lds8_store_packed(const uint32_t (&T)[8], const uint32_t (&R)[8], lds_u32* s_key,
                                                   lds_u16* s_tok) {
   if constexpr (K0 < K1) {
-    s_key[K0 * NT + threadIdx.x] = m16::lds8_key<K0>(R);
-    s_tok[K0 * NT + threadIdx.x] = (uint16_t)m16::half<K0>(T);
+    s_key[K0 * NT + threadIdx.x] = mpk::lds8_key<K0>(R);
+    s_tok[K0 * NT + threadIdx.x] = (uint16_t)mpk::half<K0>(T);
     lds8_store_packed<K0 + 1, K1, NT>(T, R, s_key, s_tok);
   }
 }
-template <int K0, int K1>
-__device__ __forceinline__ void store_packed_ids(const uint32_t (&T)[8], uint32_t m, uint32_t* out) {
+template <int K0, int K1, int ND>
+__device__ __forceinline__ void store_packed_ids(const uint32_t (&T)[ND], uint32_t m, uint32_t* out) {
   if constexpr (K0 < K1) {
-    if ((uint32_t)K0 < m) out[K0] = m16::half<K0>(T);
+    if ((uint32_t)K0 < m) out[K0] = mpk::half<K0>(T);
     store_packed_ids<K0 + 1, K1>(T, m, out);
   }
 }
-template <int K0, int K1>
-__device__ __forceinline__ void store_packed_ids(const uint32_t (&T)[16], uint32_t m, uint32_t* out) {
-  if constexpr (K0 < K1) {
-    if ((uint32_t)K0 < m) out[K0] = m32::half<K0>(T);
-    store_packed_ids<K0 + 1, K1>(T, m, out);
-  }
+
+// A piece with a byte char absent from the vocabulary (dropped by the reference) is left to the
+// generic pass: piece at byte s, ordinal o, n bytes appended to mid_list, the overflow bit when full.
+__device__ __forceinline__ void defer_to_generic(const Work& w, uint32_t s, uint32_t o, uint32_t n) {
+  const uint32_t mi = atomicAdd(&w.counters[4], 1u);
+  if (mi < w.mid_cap)
+    w.mid_list[mi] = (uint64_t)s | ((uint64_t)o << 32) | ((uint64_t)n << 48);
+  else
+    atomicOr(&w.counters[kCtrOverflow], 1u);
 }
 
 // Workgroup-shared scratch of a merge pass.
@@ -1525,7 +1527,7 @@ struct PassLds {
 // is shared by the passes of one kernel).
 // L8: the <= 8-token tier runs in LDS (merge_lds8, narrow vocabularies; s_key / s_tok its state).
 // PK (N = 16 or 32, L8): the 16-slot tier, and at N = 32 the 32-slot tier before it, keep tokens
-// and values as u16 pairs (merge16_hd.h, merge32_hd.h; tables whose values all fit,
+// and values as u16 pairs (merge_packed_hd.h; tables whose values all fit,
 // Tables::short_packed).
 // LA: the pipeline loads the next piece's text one block ahead (N / 4 + 1 registers held through the
 // merges); without it only the list entry is looked ahead and a piece loads its own text.
@@ -1618,12 +1620,27 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
         const uint32_t s = tile * kTile + (e & 0xFFFu);
         const uint32_t o = ent_ord(e);
         const uint32_t n = ent_len(e);
+        // ids go to the next free slots of the tile's region for this class (dense: a wave's
+        // stores fill whole lines), the record points at them
+        uint32_t pos = 0;
+        auto out_of = [&](uint32_t mm) {
+          pos = atomicAdd(&S.tsum[kt], mm);
+          return w.scratch + (size_t)tile * kTileSlots + pos;
+        };
+        auto record = [&](uint32_t m) {
+          CTOK_CHECK_REC(m >= 1 && m <= n && pos + m <= (uint32_t)kTileSlots && o < (uint32_t)kTileSlots,
+                         "[ctok check] class pass N=%d PK=%d tile %u: record m=%u n=%u pos=%u ordinal=%u\n", N, (int)PK,
+                         tile, m, n, pos, o);
+          w.mrec[(size_t)tile * kTileSlots + o] = rec_short(m, pos);
+          st_bytes += n;
+          st_ids += m;
+        };
         if constexpr (PK) {
           static_assert((N == 16 || N == 32) && L8 && COMPACT,
                         "the packed tiers are the 9..16 B and 17..32 B passes', ahead of merge_lds8, on compact tables");
           // packed tokens straight from the byte -> id table, packed values from the byte-pair
           // table (no entry of it panics and every value fits 16 bits: Tables::short_packed;
-          // kNoRank's low half is m16::kNone)
+          // kNoRank's low half is mpk::kNone)
           constexpr int ND = N / 2;
           uint32_t T[ND], R[ND], bytes[N];
           bool missing = false;
@@ -1633,15 +1650,11 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
           for (int d = 0; d < ND; d++) {
             const int32_t i0 = s_b2id[bytes[2 * d]], i1 = s_b2id[bytes[2 * d + 1]];
             missing |= (((uint32_t)(2 * d) < n) & (i0 < 0)) | (((uint32_t)(2 * d + 1) < n) & (i1 < 0));
-            T[d] = m16::pack2((uint32_t)i0, (uint32_t)i1);
+            T[d] = mpk::pack2((uint32_t)i0, (uint32_t)i1);
           }
           if (missing) {  // a byte char absent from the vocab is dropped: generic path
             hook();
-            const uint32_t mi = atomicAdd(&w.counters[4], 1u);
-            if (mi < w.mid_cap)
-              w.mid_list[mi] = (uint64_t)s | ((uint64_t)o << 32) | ((uint64_t)n << 48);
-            else
-              atomicOr(&w.counters[kCtrOverflow], 1u);
+            defer_to_generic(w, s, o, n);
             return;
           }
           {
@@ -1652,22 +1665,17 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
 #pragma unroll
             for (int k = 0; k < N - 1; k++) v[k] = (uint32_t)k + 1 < n ? v[k] : kNoRank;
 #pragma unroll
-            for (int d = 0; d < ND; d++) R[d] = m16::pack2(v[2 * d], v[2 * d + 1]);
+            for (int d = 0; d < ND; d++) R[d] = mpk::pack2(v[2 * d], v[2 * d + 1]);
           }
           uint32_t m = n;
           Lookup16<HOT> lk{t, P, err};
-          uint32_t pos = 0;
-          auto out_of = [&](uint32_t mm) {
-            pos = atomicAdd(&S.tsum[kt], mm);
-            return w.scratch + (size_t)tile * kTileSlots + pos;
-          };
           if constexpr (N == 32) {
             // 32 slots down to <= 16 tokens, then the 16-slot tier on the low 8 + 8 dwords
-            bool more = m32::tier(T, R, m, 16u, lk);
+            bool more = mpk::tier(T, R, m, 16u, lk);
             uint32_t T8[8], R8[8];
-            m32::low_half(T, T8);
-            m32::low_half(R, R8);
-            if (more) more = m16::tier(T8, R8, m, 8u, lk);
+            mpk::low_half(T, T8);
+            mpk::low_half(R, R8);
+            if (more) more = mpk::tier(T8, R8, m, 8u, lk);
             hook();
             if (more) {
               lds8_store_packed<0, 8, NT>(T8, R8, s_key, s_tok);
@@ -1678,7 +1686,7 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
               store_packed_ids<0, 16>(T8, m, out_of(m));
             }
           } else {
-            const bool more = m16::tier(T, R, m, 8u, lk);
+            const bool more = mpk::tier(T, R, m, 8u, lk);
             hook();
             if (more) {
               lds8_store_packed<0, 8, NT>(T, R, s_key, s_tok);
@@ -1687,11 +1695,7 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
               store_packed_ids<0, N>(T, m, out_of(m));
             }
           }
-          CTOK_CHECK_REC(m >= 1 && m <= n && pos + m <= (uint32_t)kTileSlots && o < (uint32_t)kTileSlots,
-                         "[ctok check] packed class pass N=%d tile %u: record m=%u n=%u pos=%u ordinal=%u\n", N, tile, m, n, pos, o);
-          w.mrec[(size_t)tile * kTileSlots + o] = rec_short(m, pos);
-          st_bytes += n;
-          st_ids += m;
+          record(m);
           return;
         }
         uint32_t tk[N], rk[N];
@@ -1706,11 +1710,7 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
         }
         if (missing) {  // a byte char absent from the vocab is dropped: generic path
           hook();
-          const uint32_t mi = atomicAdd(&w.counters[4], 1u);
-          if (mi < w.mid_cap)
-            w.mid_list[mi] = (uint64_t)s | ((uint64_t)o << 32) | ((uint64_t)n << 48);
-          else
-            atomicOr(&w.counters[kCtrOverflow], 1u);
+          defer_to_generic(w, s, o, n);
           return;
         }
         // initial pair ranks: every initial pair is a byte pair, one load each from the 256 x 256
@@ -1739,14 +1739,7 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
         if constexpr (N >= 16) {
           if (more) more = merge_slots<16, COMPACT, HOT, L8>(t, P, tk, rk, m, 8, err);
         }
-        // ids go to the next free slots of the tile's region for this class (dense: a wave's
-        // stores fill whole lines), the record points at them
         hook();
-        uint32_t pos = 0;
-        auto out_of = [&](uint32_t mm) {
-          pos = atomicAdd(&S.tsum[kt], mm);
-          return w.scratch + (size_t)tile * kTileSlots + pos;
-        };
         if (L8 && more) {
           m = merge_lds8<COMPACT, HOT, NT>(t, P, tk, rk, m, s_key, s_tok, err, out_of);
         } else {
@@ -1756,11 +1749,7 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
           for (int k = 0; k < N; k++)
             if ((uint32_t)k < m) out[k] = tk[k];
         }
-        CTOK_CHECK_REC(m >= 1 && m <= n && pos + m <= (uint32_t)kTileSlots && o < (uint32_t)kTileSlots,
-                       "[ctok check] class pass N=%d tile %u: record m=%u n=%u pos=%u ordinal=%u\n", N, tile, m, n, pos, o);
-        w.mrec[(size_t)tile * kTileSlots + o] = rec_short(m, pos);
-        st_bytes += n;
-        st_ids += m;
+        record(m);
     };
     if constexpr (N > 32) {
       // 64 slots: no registers to spare for a pipeline; a static stride over the chunk
@@ -2046,11 +2035,7 @@ __device__ __forceinline__ void sparse_c3(const Work& w, const Tables& t, const 
     const uint32_t b1 = lane + 1 < len ? w.text[s + lane + 1] : 0u;
     const int32_t id = s_b2id[b0];
     if (__ballot(lane < len && id < 0)) {  // a byte char absent from the vocab: the generic pass drops it
-      if (lane == 0) {
-        const uint32_t mi = atomicAdd(&w.counters[4], 1u);
-        if (mi < w.mid_cap) w.mid_list[mi] = (uint64_t)s | ((uint64_t)o << 32) | ((uint64_t)len << 48);
-        else atomicOr(&w.counters[kCtrOverflow], 1u);
-      }
+      if (lane == 0) defer_to_generic(w, s, o, len);
       continue;
     }
     uint32_t rk = lane + 1 < len ? t.pair0[(b0 << 8) | b1] : kNoRank;
@@ -2116,7 +2101,7 @@ __global__ __launch_bounds__(64 * kSparseWaves) void k_bpe_sparse(Work w, Tables
 // profiles/r05/v17_ab_mid768_c4_c5.txt).
 template <int CLS> struct MidCfg { static constexpr int KT = kMidKT; };
 
-// PK (CLS = 2, Tables::mid_packed): the 32- and 16-slot tiers on u16 pairs (merge32_hd.h).
+// PK (CLS = 2, Tables::mid_packed): the 32- and 16-slot tiers on u16 pairs (merge_packed_hd.h).
 template <bool COMPACT, int CLS, bool NARROW, uint32_t NT = 512, bool PK = false>
 __global__ __launch_bounds__(NT) void k_bpe_mid(Work w, Tables t) {
   static_assert(!PK || (CLS == 2 && NARROW && COMPACT), "the packed tiers need the narrow tables and compact values");

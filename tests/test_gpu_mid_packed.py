@@ -1,6 +1,6 @@
 """The 17..32 B pass by each of its arms, against the C oracle (CTOK_MID_PACKED, read when the
 tokenizer's device tables are made): 0 the 32 + 32 register tier in k_bpe_mid<2>, 1 the packed
-tier (tokens and pair values as u16 pairs, csrc/merge32_hd.h) in k_bpe_mid<2>, 2 the packed tier
+tier (tokens and pair values as u16 pairs, csrc/merge_packed_hd.h) in k_bpe_mid<2>, 2 the packed tier
 as the third pass of k_bpe_short when the call has no long piece (else as 1).  The packed arms
 exist for narrow compact tables whose values all fit 16 bits (the gpt2_50k fixture, the 65,535-id
 prefix of llama3); a table without the property (the shuffled-merges table, whose values are
@@ -11,7 +11,6 @@ fixture's common letters (deep merges), periodic strings (equal pairs repeated, 
 rule decides), digit runs, consonant strings (they stop merging above 16 tokens) and one document
 whose 17..32 B pieces lie across pre-tokenizer tile ends."""
 import json
-import os
 import random
 
 import numpy as np
@@ -20,49 +19,20 @@ import pytest
 from complexity_tokenizer import Tokenizer
 from datagen import corpus
 from oracle import ref_c
-from tests import id16_cases, toys
+from tests import id16_cases, packed_cases, toys
+from tests.packed_cases import TILE, env as _env
 from tests.test_gpu_parity import assert_same
 
 pytestmark = pytest.mark.gpu
 
-TILE = 3968  # bytes per pre-tokenizer tile (csrc/ctok_internal.h kTile)
 DEFAULT_ARM = 2  # csrc/ctok_internal.h kMidPackedDefault
 ARMS = [None, "0", "1", "2"]
 ARM_IDS = ["default", "register", "packed_mid", "packed_fold"]
 PACKED_TABLES = ("gpt2", "trunc65535")
 
 
-def _tile_end_doc(rng):
-    """Pieces of 17..32 B (a space and letters) starting 1, n / 2 and n - 1 bytes before a tile end."""
-    parts, pos = [], 0
-    for n in range(17, 33):
-        for delta in (1, n // 2, n - 1):
-            target = (pos // TILE + 1) * TILE - delta
-            if target - pos < 4:
-                target += TILE
-            parts.append((" ab" * (target - pos))[:target - pos])
-            parts.append(" " + "".join(rng.choice("etaoinshr") for _ in range(n - 1)))
-            pos = target + n
-    return "".join(parts)
-
-
 def _docs(seed):
-    rng = random.Random(seed)
-    docs = [_tile_end_doc(rng)]
-    for rep in range(12):
-        for n in range(17, 33):  # piece length, the leading space included
-            k = n - 1
-            words = ["".join(rng.choice("etaoinshrdlu") for _ in range(k)) for _ in range(4)]
-            words.append(("ab" * k)[:k])
-            words.append(("abc" * k)[:k])
-            words.append(rng.choice("aeo=-.") * k)
-            words.append("".join(rng.choice("0123456789") for _ in range(k)))
-            words.append("".join(rng.choice("qxzjkvwbfg") for _ in range(k)))
-            words.append("".join(rng.choice("etaoinshrdlu") for _ in range(k - 1)) + rng.choice("QXZ"))
-            rng.shuffle(words)
-            # (the first word has no leading space: one letter more keeps it at n bytes)
-            docs.append(rng.choice("etaoin") + " ".join(words))
-    return docs
+    return packed_cases.docs(seed, 17, 33, 12)
 
 
 def _class2_lengths(docs):
@@ -73,24 +43,6 @@ def _class2_lengths(docs):
             if 17 <= len(p) <= 32:
                 cnt[len(p)] += 1
     return cnt
-
-
-class _env:
-    def __init__(self, k, v):
-        self.k, self.v = k, v
-
-    def __enter__(self):
-        self.old = os.environ.get(self.k)
-        if self.v is None:
-            os.environ.pop(self.k, None)
-        else:
-            os.environ[self.k] = self.v
-
-    def __exit__(self, *a):
-        if self.old is None:
-            os.environ.pop(self.k, None)
-        else:
-            os.environ[self.k] = self.old
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """The 9..16 B pass of k_bpe_short by either 16-slot tier, against the C oracle: the packed tier
-(tokens and pair values as u16 pairs, csrc/merge16_hd.h; taken on narrow compact tables whose
+(tokens and pair values as u16 pairs, csrc/merge_packed_hd.h; taken on narrow compact tables whose
 values all fit 16 bits, as the gpt2_50k fixture's) and the 16 + 16 register tier
 (CTOK_SHORT_PACKED=0, read when the tokenizer's device tables are made; also what a table that
 fails the property gets: the shuffled-merges table, whose values are ranks, and the 128k-vocabulary
@@ -8,8 +8,6 @@ words over the fixture's common letters (deep merges), periodic strings (equal p
 the leftmost rule decides), digit runs, consonant strings (they stop merging above 8 tokens) and
 one document whose 9..16 B pieces lie across pre-tokenizer tile ends."""
 import json
-import os
-import random
 
 import numpy as np
 import pytest
@@ -17,45 +15,15 @@ import pytest
 from complexity_tokenizer import Tokenizer
 from datagen import corpus
 from oracle import ref_c
-from tests import toys
+from tests import packed_cases, toys
+from tests.packed_cases import env as _env
 from tests.test_gpu_parity import assert_same
 
 pytestmark = pytest.mark.gpu
 
-TILE = 3968  # bytes per pre-tokenizer tile (csrc/ctok_internal.h kTile)
-
-
-def _tile_end_doc(rng):
-    """Pieces of 9..16 B (a space and letters) starting 1, n / 2 and n - 1 bytes before a tile end."""
-    parts, pos = [], 0
-    for n in range(9, 17):
-        for delta in (1, n // 2, n - 1):
-            target = (pos // TILE + 1) * TILE - delta
-            if target - pos < 4:
-                target += TILE
-            parts.append((" ab" * (target - pos))[:target - pos])
-            parts.append(" " + "".join(rng.choice("etaoinshr") for _ in range(n - 1)))
-            pos = target + n
-    return "".join(parts)
-
 
 def _docs(seed):
-    rng = random.Random(seed)
-    docs = [_tile_end_doc(rng)]  # first: its offsets are the batch's
-    for rep in range(40):
-        for n in range(9, 17):  # piece length, the leading space included
-            k = n - 1
-            words = ["".join(rng.choice("etaoinshrdlu") for _ in range(k)) for _ in range(4)]
-            words.append(("ab" * k)[:k])
-            words.append(("abc" * k)[:k])
-            words.append(rng.choice("aeo=-.") * k)
-            words.append("".join(rng.choice("0123456789") for _ in range(k)))
-            words.append("".join(rng.choice("qxzjkvwbfg") for _ in range(k)))
-            words.append("".join(rng.choice("etaoinshrdlu") for _ in range(k - 1)) + rng.choice("QXZ"))
-            rng.shuffle(words)
-            # (the first word has no leading space: one letter more keeps it at n bytes)
-            docs.append(rng.choice("etaoin") + " ".join(words))
-    return docs
+    return packed_cases.docs(seed, 9, 17, 40)
 
 
 @pytest.fixture(scope="module")
@@ -79,24 +47,6 @@ def tables(gpt2_path, llama3_path):
         return cache[name]
 
     return get
-
-
-class _env:
-    def __init__(self, k, v):
-        self.k, self.v = k, v
-
-    def __enter__(self):
-        self.old = os.environ.get(self.k)
-        if self.v is None:
-            os.environ.pop(self.k, None)
-        else:
-            os.environ[self.k] = self.v
-
-    def __exit__(self, *a):
-        if self.old is None:
-            os.environ.pop(self.k, None)
-        else:
-            os.environ[self.k] = self.old
 
 
 @pytest.mark.parametrize("packed", [None, "0"], ids=["default", "packed_off"])
