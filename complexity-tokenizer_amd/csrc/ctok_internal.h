@@ -1,5 +1,5 @@
-// Internal interfaces between the C++ host runtime (ctok_host.cpp) and the HIP kernels
-// (kernels.hip).  Not part of the C ABI.
+// Internal interfaces between the C++ host runtime (ctok_encode.cpp, ctok_host.cpp) and the HIP
+// kernels (kernels.hip).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,12 +44,18 @@ constexpr int kCounterWords = kNumCounters + kC3Shards;
 // counters[] slots of class pass c: bytes merged / ids produced (statistics), next chunk
 __host__ __device__ constexpr int ctr_stat(int c) { return c < 3 ? 6 + 2 * c : 16; }
 __host__ __device__ constexpr int ctr_chunk(int c) { return c < 3 ? 13 + c : 18; }
+constexpr int kCtrLong = 0;      // counters[0]: long-list entries appended (k_segment; past long_cap none was stored)
+constexpr int kCtrErr = 2;       // counters[2]: error bits (kErrPanic)
+constexpr int kCtrNfcDocs = 3;   // counters[3]: documents k_nfc_check flagged
+constexpr int kCtrDropped = 4;   // counters[4]: dropped-byte list (mid_list) entries appended
+constexpr int kCtrPieces = 5;    // counters[5]: pieces (statistics)
+constexpr int kCtrNfcFlag = 12;  // counters[12] != 0: nfc_watch and k_segment saw a code point NFC might change
 constexpr int kCtrAnyMid = 19;  // counters[19] != 0: some tile has a class-2 piece
 constexpr int kCtrAnyC3 = 20;   // counters[20] != 0: some tile has a class-3 piece
 constexpr int kCtrEmptyDocs = 21;  // counters[21]: empty documents (k_tilefirst); 0: k_emit writes tok_off
 constexpr int kCtrC3Count = 22;    // counters[22] of the report: class-3 pieces (the shards' sum)
 constexpr int kCtrC3Take = 23;     // counters[23]: next piece of the sparse class-3 pass
-constexpr uint32_t kC3SparseDefault = 65536;  // the most pieces the sparse class-3 path takes by default (ctok_host.cpp)
+constexpr uint32_t kC3SparseDefault = 65536;  // the most pieces the sparse class-3 path takes by default (call_plan.h)
 constexpr uint32_t kWgRecWords = 4 * 1024 * 4;  // Work::wgrec: 4 kernels x 1024 workgroups x 4 words
 constexpr int kMidPackedDefault = 2;           // the 17..32 B pass of short_packed tables (CTOK_MID_PACKED, Tables::mid_packed)
 constexpr int kOverlapDefault = 1;            // merge passes on the side stream without long pieces (CTOK_OVERLAP)
@@ -163,7 +169,7 @@ __host__ __device__ inline uint32_t piece_hash(uint32_t lo, uint32_t hi, uint32_
 // Common non-ASCII blocks classified by range tests instead of the two-level tables (C5: CJK,
 // kana, Hangul, emoji): the class (1 = L, 3 = other) when cp lies in one, else -1.  Every code
 // point of these ranges has that class and no NFC flag in the generated tables; the host checks
-// this once (cp_fast_ok, ctok_host.cpp) and clears Tables::cp_fast otherwise.
+// this once (cp_fast_ok, ctok_encode.cpp) and clears Tables::cp_fast otherwise.
 __host__ __device__ __forceinline__ int cp_range_class(uint32_t cp) {
   if (cp - 0x4E00u < 0x5200u) return 1;    // CJK Unified Ideographs U+4E00..U+9FFF (Lo)
   if (cp - 0xAC00u < 0x2BA4u) return 1;    // Hangul Syllables U+AC00..U+D7A3 (Lo)
@@ -232,7 +238,7 @@ struct Tables {            // device pointers, owned by the host runtime
 };
 
 // Does k_bpe_short take the 17..32 B class as its third pass?  The one decision of both sides, from
-// one value: long_pieces is counters[0], final once k_segment has completed -- the kernel reads it
+// one value: long_pieces is counters[kCtrLong], final once k_segment has completed -- the kernel reads it
 // on the device, the host in the report (the same word, copied by the kernel's first wave).  The
 // host launches k_bpe_mid<2> exactly when this is false.
 __host__ __device__ inline bool mid_folded(const Tables& t, uint32_t long_pieces) {
@@ -249,7 +255,7 @@ struct Work {              // device pointers, sized by the host for one call
   uint32_t n_words;
   uint32_t n_tiles;
   uint32_t n_cus;          // compute units of the device (persistent merge-pass grid)
-  uint32_t nfc_watch;      // 1, 2: the text was not NFC-checked; k_segment sets counters[12] on a
+  uint32_t nfc_watch;      // 1, 2: the text was not NFC-checked; k_segment sets counters[kCtrNfcFlag] on a
                            // code point NFC might change; 1: the later passes then stop (the call
                            // runs again normalised), 2: they finish (the flagged docs are spliced)
   uint32_t* nfc_bits;      // nfc_watch: bit g set when 64-byte word g holds the start of a code point
@@ -289,10 +295,9 @@ struct Work {              // device pointers, sized by the host for one call
   uint64_t* long_list;     // pieces > kMedMax B (> kShortMax B in generic mode), or of unknown length
                            // at a tile end: s | j << 32
   uint64_t* mid_list;      // pieces with dropped bytes for the generic kernel: s | j << 32 | n << 48
-  uint32_t* counters;      // [kNumCounters] [0] long count, [2] err, [3] nfc docs, [4] mid count,
-                           // [5] pieces (stats), [ctr_stat(c)], [ctr_stat(c) + 1]: bytes merged /
-                           // ids produced by class pass c (stats), [12] NFC speculation failed,
-                           // [ctr_chunk(c)] next chunk of class pass c, [kCtrAnyMid], [kCtrAnyC3]
+  uint32_t* counters;      // [kCounterWords] the kCtr* slots, [ctr_stat(c)], [ctr_stat(c) + 1]: bytes merged /
+                           // ids produced by class pass c (stats), [ctr_chunk(c)] next chunk of class pass c;
+                           // then the class-3 shard counts
   uint32_t* lw;            // global-memory long-piece state (4 u32 per byte of the pieces > 4 KiB), sized after k_long_len
   uint32_t* scan_tmp;      // scan partials
   uint64_t scan_tmp_cap;
@@ -394,7 +399,7 @@ void upload_done();
 // also zeroes the counters and nfc_bits; x: k_clear's launch options, x2: k_tilefirst's
 hipError_t launch_docstart(const Work& w, hipStream_t s, bool zero_counters, Lx x = {}, Lx x2 = {});
 uint64_t nfc_bits_words(uint64_t n_bytes);  // nfc_bits size (u32 words)
-// tile_tok, tile_doc: exclusive scans + totals at n_tiles; count: pieces into counters[5]; x: the first launch's
+// tile_tok, tile_doc: exclusive scans + totals at n_tiles; count: pieces into counters[kCtrPieces]; x: the first launch's
 hipError_t scan_tiles(const Work& w, hipStream_t s, bool count, Lx x = {});
 hipError_t launch_nfc_check(const uint8_t* text, uint64_t n_bytes, const uint64_t* doc_off, uint32_t n_docs,
                             const Tables& t, uint32_t* doc_flag, uint32_t* counter, hipStream_t s);
@@ -418,7 +423,7 @@ hipError_t launch_long_prep(const Work& w, const Tables& t, hipStream_t s, uint3
 // long-piece tiers (side stream): n_long = k_segment's long-list length, any_c3 = a class-3
 // piece exists (the side instance of the 33..64 B pass); grids sized for them, nothing when empty
 hipError_t launch_bpe_long(const Work& w, const Tables& t, hipStream_t s, uint32_t n_long, bool any_c3, bool any_gmem);
-// count_pieces: counters[5] = pieces (statistics); empty_docs: some document is empty (k_tokoff
+// count_pieces: counters[kCtrPieces] = pieces (statistics); empty_docs: some document is empty (k_tokoff
 // then writes every tok_off entry; else k_emit wrote them and k_tokoff only the total)
 // (first: the tile scan's first launch; last: k_tokoff)
 hipError_t launch_emit(const Work& w, uint32_t* ids, uint64_t ids_cap, uint64_t* tok_off, hipStream_t s,

@@ -1,5 +1,6 @@
-// Internal interfaces of the host runtime shared by its translation units (ctok_host.cpp defines
-// them; trainer_host.cpp uses them).  Not part of the C ABI.
+// What the tokenizer's host runtime offers the trainer's (ctok_host.cpp defines it;
+// trainer_host.cpp uses it).  Not part of the C ABI.  The tokenizer runtime's own shared
+// internals are in host_internal.h.
 #pragma once
 #include <cstdint>
 #include <functional>

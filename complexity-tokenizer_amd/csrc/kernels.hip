@@ -187,7 +187,7 @@ __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_re
 
 // Diagnostic (CTOK_WGREC=1, Work::wgrec non-null): workgroup `blockIdx.x` of kernel slot k records
 // its start and end (wall clock, 100 MHz), its CU (xcc | se | cu) and a count.  The host prints,
-// per kernel, the CUs used and the spread of the workgroups' starts and ends (ctok_host.cpp).
+// per kernel, the CUs used and the spread of the workgroups' starts and ends (ctok_encode.cpp).
 constexpr uint32_t kWgRecMax = 1024;  // (4 kernel slots: short, mid<2>, mid<3>, sparse)
 // (stateless: the record's place is recomputed at the end from the kernel argument, so that no
 // register stays live across the kernel -- the 64-slot pass is at its register limit)
@@ -211,11 +211,11 @@ struct WgRec {
 // NFC speculation failed in k_segment (a code point NFC might change): the rest of this pass is
 // discarded (the host checks, normalises and runs the pipeline again), so the kernels after
 // k_segment return at once instead of merging text that will be re-encoded.
-__device__ __forceinline__ bool spec_failed(const Work& w) { return w.nfc_watch == 1 && uni(w.counters[12]) != 0; }
+__device__ __forceinline__ bool spec_failed(const Work& w) { return w.nfc_watch == 1 && uni(w.counters[kCtrNfcFlag]) != 0; }
 
 // pieces in the long list (k_segment counts them all; past long_cap they were not stored and the
 // host reruns the call with the safe capacities)
-__device__ __forceinline__ uint32_t long_count(const Work& w) { return min(w.counters[0], w.long_cap); }
+__device__ __forceinline__ uint32_t long_count(const Work& w) { return min(w.counters[kCtrLong], w.long_cap); }
 
 // wave-aggregated append to an LDS counter: returns this lane's slot (lanes with take == false
 // get garbage).  One ds_add per wave instead of one per lane.
@@ -688,7 +688,7 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
       }
     }
     if (nfc_bad && w.nfc_watch) {
-      atomicOr(&w.counters[12], 1u);
+      atomicOr(&w.counters[kCtrNfcFlag], 1u);
       if (w.nfc_watch == 2 && g >= 0) atomicOr(&w.nfc_bits[g >> 5], 1u << (g & 31));  // (splice mode only)
     }
   }
@@ -910,7 +910,7 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
       } else if (lm) {  // (past kSegLongCap long pieces in the tile: one global atomic per wave)
         const uint32_t leader = __ffsll((unsigned long long)lm) - 1;
         uint32_t b = 0;
-        if (lane == leader) b = atomicAdd(&w.counters[0], (uint32_t)__popcll(lm));
+        if (lane == leader) b = atomicAdd(&w.counters[kCtrLong], (uint32_t)__popcll(lm));
         b = __builtin_amdgcn_readlane(b, leader);
         const uint32_t li = b + __popcll(lm & lanemask_lt());
         if (cls[u] == 3 && li < w.long_cap)
@@ -930,7 +930,7 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
   }
   if (nlong) {  // the tile's staged long pieces: one reservation, coalesced entry stores
     uint32_t b = 0;
-    if (lane == 0) b = atomicAdd(&w.counters[0], nlong);
+    if (lane == 0) b = atomicAdd(&w.counters[kCtrLong], nlong);
     b = __builtin_amdgcn_readfirstlane(b);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1126,11 +1126,11 @@ __global__ __launch_bounds__(MID ? 128 : 256) void k_bpe_generic(Work w, Tables 
   __shared__ uint32_t s_pre[kTilesGeneric + 1], s_tsum[kTilesGeneric];
   const uint32_t tid = threadIdx.x;
   for (uint32_t i = tid; i < 256; i += NT) s_b2id[i] = t.byte2id[i];
-  uint32_t* err = &w.counters[2];
+  uint32_t* err = &w.counters[kCtrErr];
   uint32_t E, t0 = 0;
   if (MID) {
     __syncthreads();
-    E = min(w.counters[4], w.mid_cap);
+    E = min(w.counters[kCtrDropped], w.mid_cap);
   } else {
     t0 = blockIdx.x * kTilesGeneric;
     E = tile_share_init<kTilesGeneric>(w.tcls, w.n_tiles, t0, s_pre, s_tsum);
@@ -1502,7 +1502,7 @@ __device__ __forceinline__ void store_packed_ids(const uint32_t (&T)[ND], uint32
 // A piece with a byte char absent from the vocabulary (dropped by the reference) is left to the
 // generic pass: piece at byte s, ordinal o, n bytes appended to mid_list, the overflow bit when full.
 __device__ __forceinline__ void defer_to_generic(const Work& w, uint32_t s, uint32_t o, uint32_t n) {
-  const uint32_t mi = atomicAdd(&w.counters[4], 1u);
+  const uint32_t mi = atomicAdd(&w.counters[kCtrDropped], 1u);
   if (mi < w.mid_cap)
     w.mid_list[mi] = (uint64_t)s | ((uint64_t)o << 32) | ((uint64_t)n << 48);
   else
@@ -1541,7 +1541,7 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
   static_assert(KT <= (int)NT, "a thread per chunk tile");
   static_assert(KT <= SKT, "the shared scratch holds the pass's chunk");
   const uint32_t tid = threadIdx.x;
-  uint32_t* err = &w.counters[2];
+  uint32_t* err = &w.counters[kCtrErr];
   const uint32_t* list = class_list<N>(w);
   const uint32_t cap = class_cap<N>(w);
   const uint32_t* counts = w.tcls + (size_t)LC::cls * w.n_tiles;
@@ -1941,7 +1941,7 @@ __global__ __launch_bounds__(1024) void k_bpe_short(Work w, Tables t, uint32_t p
       // one read for the workgroup, handed round through LDS: every thread takes the same branch,
       // so all 1024 reach class_pass's barriers or none does.  (S.next is free here: the passes
       // above end with a barrier, and class_pass writes it only after its first one.)
-      if (tid == 0) S.next = (mid_folded(t, w.counters[0]) && w.counters[kCtrAnyMid] != 0) ? 1u : 0u;
+      if (tid == 0) S.next = (mid_folded(t, w.counters[kCtrLong]) && w.counters[kCtrAnyMid] != 0) ? 1u : 0u;
       __syncthreads();
       const uint32_t fold = S.next;
       if (fold)
@@ -2018,7 +2018,7 @@ __device__ __forceinline__ void sparse_c3(const Work& w, const Tables& t, const 
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t cap = w.c3_max / kC3Shards;
   const uint32_t pre = w.c3pre[lane];  // (kC3Shards == 64: shard `lane`'s first piece)
-  uint32_t* err = &w.counters[2];
+  uint32_t* err = &w.counters[kCtrErr];
   uint32_t st_bytes = 0, st_ids = 0;
   for (;;) {
     // (every lane takes part, lane 0 adding 1: no divergent branch around the atomic)
@@ -2190,10 +2190,11 @@ static hipError_t launch_short_t(const Work& w, const Tables& t, hipStream_t s, 
   if (!w.n_tiles) return hipSuccess;
   // (Work::short_wgs: fewer workgroups than CUs leave CUs to the side stream's passes from the start)
   const uint32_t grid = min((w.n_tiles + w.unit - 1) / w.unit, w.short_wgs ? min(w.short_wgs, w.n_cus) : w.n_cus);
-  if (t.dbg == 30) {
-    k_bpe_short<C, NW, PK, PK32><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 1u);
-    k_bpe_short<C, NW, PK, PK32><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 2u);
-    if (PK32) k_bpe_short<C, NW, PK, PK32><<<grid, ShortCfg<NW>::NT, kLdsImageBytes, s>>>(w, t, 4u);
+  if (t.dbg == 30) {  // a launch per pass: the first records x.start, the last x.stop
+    const uint32_t last = PK32 ? 4u : 2u;
+    for (uint32_t pass = 1u; pass <= last; pass <<= 1)
+      launch_lx(Lx{pass == 1u ? x.start : nullptr, pass == last ? x.stop : nullptr}, k_bpe_short<C, NW, PK, PK32>, grid,
+                ShortCfg<NW>::NT, kLdsImageBytes, s, w, t, pass);
   } else {
     launch_lx(x, k_bpe_short<C, NW, PK, PK32>, grid, ShortCfg<NW>::NT, kLdsImageBytes, s, w, t, PK32 ? 7u : 3u);
   }
@@ -2478,7 +2479,7 @@ __global__ __launch_bounds__(256) void k_bpe_long(Work w, Tables t) {
   const uint32_t wid = uni(threadIdx.x >> 6);
   const uint32_t n_long = uni(long_count(w));
   const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
-  uint32_t* err = &w.counters[2];
+  uint32_t* err = &w.counters[kCtrErr];
   for (uint32_t li = uni(blockIdx.x * (blockDim.x >> 6) + wid); li < n_long; li += n_waves) {
     const uint64_t e = w.long_list[li];
     const uint32_t s = uni((uint32_t)e);
@@ -3329,7 +3330,7 @@ __global__ __launch_bounds__(64 * NW) void k_bpe_wave(Work w, Tables t) {
   const PairLds P = HOT ? PairLds{(const lds_u64*)s_dyn, (const lds_u32*)(s_dyn + kHotBuckets)}
                         : PairLds{nullptr, (const lds_u32*)s_dyn, NOB};
   lds_u32* slice = (lds_u32*)((__attribute__((address_space(3))) uint8_t*)(s_dyn + kImg) + (size_t)wid * kSlice);
-  uint32_t* err = &w.counters[2];
+  uint32_t* err = &w.counters[kCtrErr];
   uint32_t rounds = 0;  // this wave's rounds over its pieces (statistics; one atomic at the end)
   for (uint32_t step = uni(blockIdx.x * NW + wid);; step += gridDim.x * NW) {
     uint32_t li;
@@ -3922,7 +3923,7 @@ __global__ __launch_bounds__(256) void k_tiles_reduce(Work w, uint64_t* __restri
   if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
 
-// count: also the batch's pieces (statistics only): the sum of tile_np into counters[5]
+// count: also the batch's pieces (statistics only): the sum of tile_np into counters[kCtrPieces]
 __global__ __launch_bounds__(256) void k_tiles_apply(Work w, const uint64_t* __restrict__ part_scanned, uint32_t count) {
   __shared__ uint64_t s_scan[17];
   const uint64_t n = w.n_tiles;
@@ -3953,7 +3954,7 @@ __global__ __launch_bounds__(256) void k_tiles_apply(Work w, const uint64_t* __r
     for (int k = 0; k < kTileScanPer; k++)
       if (b0 + k < n) c += w.tile_np[b0 + k];
     c = wave_sum_full_u32(c);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&w.counters[5], c);  // (counters are zeroed per call)
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&w.counters[kCtrPieces], c);  // (counters are zeroed per call)
   }
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {  // the totals at index n
     w.tile_tok[n] = (uint32_t)(base + total);
@@ -3992,7 +3993,7 @@ hipError_t scan_u64(uint64_t* inout, uint64_t n, uint64_t* tmp, uint64_t tmp_cap
 }
 
 // ------------------------------------------------------------------------------------------
-// NFC splice (ctok_host.cpp nfc_splice): after a speculative pass over raw text flagged code
+// NFC splice (ctok_encode.cpp nfc_splice): after a speculative pass over raw text flagged code
 // points NFC may change, only the documents holding them are normalised and encoded again, as a
 // sub-batch, and their ids replace the speculative pass's in the output.  rank[d] = flagged docs
 // before d (exclusive scan of the NFC-check flags; doc d is flagged when rank[d + 1] > rank[d]).

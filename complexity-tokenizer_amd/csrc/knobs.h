@@ -1,0 +1,73 @@
+// Every CTOK_* environment variable the library reads, gathered by the time it is read.
+// Host-only.  (The trainer's own variables are in trainer_host.cpp.)
+#pragma once
+#include <cstdint>
+#include <cstdlib>
+#include <optional>
+
+#include "ctok_internal.h"
+
+namespace ctok_rt __attribute__((visibility("hidden"))) {
+
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+inline int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+inline std::optional<uint64_t> env_u64(const char* name) {
+  const char* v = getenv(name);
+  return v ? std::optional<uint64_t>(strtoull(v, nullptr, 10)) : std::nullopt;
+}
+
+// Read when a tokenizer's tables are compiled (load / load_root): A/B arms of the table compiler
+struct LoadKnobs {
+  bool load_timing = env_set("CTOK_LOAD_TIMING");
+  bool force_wide = env_set("CTOK_FORCE_WIDE");
+  bool no_hot_table = env_set("CTOK_NO_HOT_TABLE");
+  bool no_window = env_set("CTOK_NO_WINDOW");
+  bool no_piece_table = env_set("CTOK_NO_PIECE_TABLE");
+  size_t merge_slack = (size_t)env_int("CTOK_MERGE_SLACK", 8);
+  size_t merge16_slack = (size_t)env_int("CTOK_MERGE16_SLACK", 64);
+  size_t piece_slack = (size_t)env_int("CTOK_PIECE_SLACK", 8);
+};
+
+// Read when the tables are uploaded to a device (device_state): what Tables says of them
+struct UploadKnobs {
+  bool force_improper = env_set("CTOK_FORCE_IMPROPER");
+  bool force_wide_slots = env_set("CTOK_FORCE_WIDE_SLOTS");
+  int short_packed = env_int("CTOK_SHORT_PACKED", 1);   // 0: the 16 + 16 register tier on every table
+  int mid_packed = env_int("CTOK_MID_PACKED", ctok_dev::kMidPackedDefault);  // Tables::mid_packed
+  uint32_t dbg_mode = (uint32_t)env_int("CTOK_DBG_MODE", 0);
+};
+
+// Read once per process, at the first use
+struct ProcessKnobs {
+  bool no_cp_ranges = env_set("CTOK_NO_CP_RANGES");
+  bool debug_sync = env_set("CTOK_DEBUG_SYNC");
+  bool safe_capacities = env_set("CTOK_SAFE_CAPACITIES");
+  bool hostprof = env_set("CTOK_HOSTPROF");
+  uint32_t unit = (uint32_t)env_int("CTOK_UNIT", 0);
+  bool rec32 = env_set("CTOK_REC32");
+  bool wgrec = env_set("CTOK_WGREC");
+  bool stamps = env_set("CTOK_STAMPS");
+  bool copy_results = env_set("CTOK_COPY_RESULTS");
+  bool no_chunk_ramp = env_set("CTOK_NO_CHUNK_RAMP");
+  bool pipe_trace = env_set("CTOK_PIPE_TRACE");
+};
+inline const ProcessKnobs& process_knobs() {
+  static const ProcessKnobs k;
+  return k;
+}
+
+// Read by every encode call (the tests flip C3_SPARSE, NFC_RERUN and WIRE32 within one process)
+struct CallKnobs {
+  bool no_nfc_speculation = env_set("CTOK_NO_NFC_SPECULATION");
+  bool nfc_rerun = env_set("CTOK_NFC_RERUN");
+  uint32_t short_wgs = (uint32_t)env_int("CTOK_SHORT_WGS", 0);
+  std::optional<uint64_t> c3_sparse = env_u64("CTOK_C3_SPARSE");  // the sparse class-3 bound (unset: the default rule)
+  bool mid512 = env_set("CTOK_MID512");
+  int overlap = env_int("CTOK_OVERLAP", ctok_dev::kOverlapDefault);  // >= 1: merge passes on the idle side stream
+  bool wire32 = env_set("CTOK_WIRE32");
+};
+
+}  // namespace ctok_rt

@@ -1,5 +1,5 @@
 """Does Rust's `regex::Regex::new` reject a Split pattern?  (Test infrastructure: the oracle's
-restatement of the decision the product makes in ctok_host.cpp `rust_regex_rejects`.)
+restatement of the decision the product makes in ctok_load.cpp `rust_regex_rejects`.)
 
 The reference compiles a Split pre-tokenizer's pattern on every call and, when `Regex::new` fails,
 returns the text unsplit (/root/reference/src/pretokenizers.rs:277-302): the Split is a no-op.  The
