@@ -415,14 +415,10 @@ class Tokenizer:
         sp = self.special_tokens
         return [1 if (self._tok_str(int(i)) is not None and self._tok_str(int(i)) in sp) else 0 for i in ids]
 
-    def encode_padded(self, texts, pairs=None, *, add_special_tokens: bool = True, truncation: bool = False,
-                      max_length: int | None = None, padding: str | None = None, pad_left: bool = False,
-                      pad_id: int | None = None, timing: bool = False, no_postprocess: bool = False) -> dict:
-        """Extension: the batch as [rows, width] uint32 arrays straight from the GPU --
-        input_ids, attention_mask, token_type_ids, special_tokens_mask, plus row_len (content +
-        padding).  padding: None, "longest" or "max_length"; pairs: a list of second texts (row r
-        = texts[r] + pairs[r]).  Semantics as encode_batch_with_padding / __call__ (include/ctok.h,
-        CTOK_P_*), without overflowing windows."""
+    def _pad_inputs(self, texts, pairs, add_special_tokens, truncation, padding, pad_left, pad_id, no_postprocess):
+        """The packed batch and the CTOK_P_* flags of a padded call, and what bounds a row's length
+        before it runs: each row's byte count (ids <= bytes unless NFC grows the text) and the
+        post-processor's $A and special item counts.  -> (text, off, n_docs, rows, flags, lens, n_a, n_s)"""
         if pairs is not None:
             if len(pairs) != len(texts):
                 raise ValueError("pairs must have one entry per text")
@@ -450,17 +446,29 @@ class Tokenizer:
             f |= _n.CTOK_P_PAD_ID
         if no_postprocess:
             f |= _n.CTOK_P_NO_POSTPROCESS
-        ml = int(max_length) if max_length is not None else self.model_max_length
-        opts = _n.PadOpts(f, int(pad_id or 0), ml)
-        # first guess of the width: ids <= bytes unless NFC grows the text (then the call reports
-        # the width it needs and runs again)
         lens = np.diff(off.astype(np.int64))
         if pairs is not None:
             lens = lens.reshape(-1, 2).sum(axis=1) if rows else lens[:0]
         items = self._pp_items() if (add_special_tokens and not no_postprocess) else None
         n_a = items.count(_n.CTOK_PP_SEQUENCE) if items is not None else 1
         n_s = len(items) - n_a if items is not None else 0
-        width = (int(lens.max()) * max(n_a, 1) + n_s + 1) if rows else 0
+        return text, off, len(docs), rows, f, lens, max(n_a, 1), n_s
+
+    def encode_padded(self, texts, pairs=None, *, add_special_tokens: bool = True, truncation: bool = False,
+                      max_length: int | None = None, padding: str | None = None, pad_left: bool = False,
+                      pad_id: int | None = None, timing: bool = False, no_postprocess: bool = False) -> dict:
+        """Extension: the batch as [rows, width] uint32 arrays straight from the GPU --
+        input_ids, attention_mask, token_type_ids, special_tokens_mask, plus row_len (content +
+        padding).  padding: None, "longest" or "max_length"; pairs: a list of second texts (row r
+        = texts[r] + pairs[r]).  Semantics as encode_batch_with_padding / __call__ (include/ctok.h,
+        CTOK_P_*), without overflowing windows (those: encode_windows)."""
+        text, off, n_docs, rows, f, lens, n_a, n_s = self._pad_inputs(texts, pairs, add_special_tokens, truncation, padding,
+                                                                      pad_left, pad_id, no_postprocess)
+        ml = int(max_length) if max_length is not None else self.model_max_length
+        opts = _n.PadOpts(f, int(pad_id or 0), ml)
+        # first guess of the width: ids <= bytes unless NFC grows the text (then the call reports
+        # the width it needs and runs again)
+        width = (int(lens.max()) * n_a + n_s + 1) if rows else 0
         if truncation:
             width = min(width, ml)
         if padding == "max_length":
@@ -472,7 +480,7 @@ class Tokenizer:
             wout = ctypes.c_uint64()
             st = _n.Stats()
             ex = _n.Exec(self.device, None, _n.CTOK_F_TIMING if timing else 0)
-            rc = _n.lib.ctok_encode_padded(self._h, text.ctypes.data, off.ctypes.data, len(docs), ctypes.byref(opts),
+            rc = _n.lib.ctok_encode_padded(self._h, text.ctypes.data, off.ctypes.data, n_docs, ctypes.byref(opts),
                                            arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data,
                                            arrs[3].ctypes.data, cap, row_len.ctypes.data, ctypes.byref(wout),
                                            ctypes.byref(ex), ctypes.byref(st))
@@ -489,6 +497,104 @@ class Tokenizer:
                zip(("input_ids", "attention_mask", "token_type_ids", "special_tokens_mask"), arrs)}
         out["row_len"] = row_len[:rows].astype(np.int64)
         return out
+
+    def encode_windows(self, texts, pairs=None, *, max_length: int | None = None, stride: int = 0,
+                       add_special_tokens: bool = True, padding: str | None = None, pad_left: bool = False,
+                       pad_id: int | None = None, no_postprocess: bool = False, timing: bool = False) -> dict:
+        """Extension: the batch cut into overflowing stride windows on the GPU
+        (Encoding::truncate_with_stride, src/encoding.rs:175-223; include/ctok.h
+        ctok_encode_windows).  A row longer than max_length becomes 1 + ceil((P - max_length) /
+        (max_length - stride)) windows, the truncated main encoding first and its `overflowing`
+        list after it; stride=0 gives plain consecutive windows.  Returns [n_windows, width]
+        uint32 arrays input_ids, attention_mask, token_type_ids, special_tokens_mask, and int64
+        row_len [n_windows] (the window's Encoding length), overflow_to_sample_mapping [n_windows]
+        (its row), window_start [n_windows] (its first position in the row) and row_window
+        [rows + 1] (row r's windows are row_window[r] .. row_window[r + 1]).  padding as
+        __call__: the main window of each row only.  stride >= max_length raises ValueError.  A row
+        that overflows with fewer tokens than ids raises PanicException, as the reference panics
+        slicing `tokens`: after a post-processor that adds ids, and with add_special_tokens=False
+        when the row holds an added token whose id is not in the vocab."""
+        ml = int(max_length) if max_length is not None else self.model_max_length
+        stride = int(stride)
+        if stride < 0 or stride >= ml:
+            raise ValueError("stride must be smaller than max_length (the reference loops forever)")
+        text, off, n_docs, rows, f, lens, n_a, n_s = self._pad_inputs(texts, pairs, add_special_tokens, True, padding,
+                                                                      pad_left, pad_id, no_postprocess)
+        opts = _n.PadOpts(f | _n.CTOK_P_WINDOWS, int(pad_id or 0), ml)
+        # first guess of the capacities from the byte lengths: ids <= bytes unless NFC grows the
+        # text (then the call reports the windows and the width it needs and runs once more)
+        bound = lens * n_a + n_s
+        step = ml - stride
+        n_win = int(np.where(bound > ml, 1 + (bound - ml + step - 1) // step, 1).sum()) if rows else 0
+        width = min(int(bound.max()) + 1, ml) if rows else 0
+        if padding == "max_length":
+            width = max(width, ml)
+        for attempt in (0, 1):
+            cap, wcap = max(n_win * width, 1), max(n_win, 1)
+            arrs = [np.empty(cap, dtype=np.uint32) for _ in range(4)]
+            win_len, win_start = np.empty(wcap, dtype=np.uint64), np.empty(wcap, dtype=np.uint64)
+            win_row = np.empty(wcap, dtype=np.uint32)
+            row_win = np.empty(rows + 1, dtype=np.uint64)
+            nout, wout = ctypes.c_uint64(), ctypes.c_uint64()
+            st = _n.Stats()
+            ex = _n.Exec(self.device, None, _n.CTOK_F_TIMING if timing else 0)
+            rc = _n.lib.ctok_encode_windows(self._h, text.ctypes.data, off.ctypes.data, n_docs, ctypes.byref(opts), stride,
+                                            arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data,
+                                            arrs[3].ctypes.data, cap, win_len.ctypes.data, win_row.ctypes.data,
+                                            win_start.ctypes.data, wcap, row_win.ctypes.data, ctypes.byref(nout),
+                                            ctypes.byref(wout), ctypes.byref(ex), ctypes.byref(st))
+            if rc == _n.CTOK_E_CAPACITY and attempt == 0:
+                n_win, width = int(nout.value), int(wout.value)
+                continue
+            if rc != _n.CTOK_OK:
+                _raise(rc)
+            break
+        self.last_stats = st.as_dict()
+        n, w = int(nout.value), int(wout.value)
+        out = {k: a[: n * w].reshape((n, w)) for k, a in
+               zip(("input_ids", "attention_mask", "token_type_ids", "special_tokens_mask"), arrs)}
+        out["row_len"] = win_len[:n].astype(np.int64)
+        out["overflow_to_sample_mapping"] = win_row[:n].astype(np.int64)
+        out["window_start"] = win_start[:n].astype(np.int64)
+        out["row_window"] = row_win.astype(np.int64)
+        return out
+
+    def encode_windows_device(self, d_text: int, d_off: int, n_docs: int, n_bytes: int, *, max_length: int, stride: int,
+                              d_ids: int, cap: int, d_win_len: int, d_win_row: int, win_cap: int, d_row_win: int,
+                              d_attention: int = 0, d_type_ids: int = 0, d_special: int = 0, d_win_start: int = 0,
+                              pairs: bool = False, add_special_tokens: bool = True, padding: str | None = None,
+                              pad_left: bool = False, pad_id: int | None = None, no_postprocess: bool = False,
+                              stream: int = 0, timing: bool = False, device: int | None = None):
+        """Extension: encode_windows on a batch and outputs already resident in HBM (raw device
+        pointers, e.g. from torch tensors' data_ptr(); 0 for an output that is not wanted among
+        the three masks and d_win_start).  The arrays hold cap cells each, the window records
+        win_cap entries, d_row_win rows + 1.  Work is ordered on `stream` (0 = the library's own).
+        Returns (n_windows, width); when they do not fit, raises ValueError whose args[1:] are
+        (n_windows, width) needed -- d_row_win is filled, nothing else is written."""
+        f = (_n.CTOK_P_ADD_SPECIAL if add_special_tokens else 0) | (_n.CTOK_P_PAIRS if pairs else 0)
+        if padding == "longest":
+            f |= _n.CTOK_P_PAD_LONGEST
+        elif padding == "max_length":
+            f |= _n.CTOK_P_PAD_TO_MAX
+        elif padding is not None:
+            raise ValueError("padding must be None, 'longest' or 'max_length'")
+        f |= (_n.CTOK_P_PAD_LEFT if pad_left else 0) | (_n.CTOK_P_PAD_ID if pad_id is not None else 0)
+        f |= (_n.CTOK_P_NO_POSTPROCESS if no_postprocess else 0) | _n.CTOK_P_WINDOWS
+        opts = _n.PadOpts(f, int(pad_id or 0), int(max_length))
+        ex = _n.Exec(self.device if device is None else device, stream or None, _n.CTOK_F_TIMING if timing else 0)
+        st = _n.Stats()
+        nout, wout = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = _n.lib.ctok_encode_windows_device(self._h, d_text, d_off, n_docs, n_bytes, ctypes.byref(opts), int(stride),
+                                               d_ids or None, d_attention or None, d_type_ids or None, d_special or None,
+                                               cap, d_win_len or None, d_win_row or None, d_win_start or None, win_cap,
+                                               d_row_win, ctypes.byref(nout), ctypes.byref(wout), ctypes.byref(ex),
+                                               ctypes.byref(st))
+        if rc == _n.CTOK_E_CAPACITY:
+            raise ValueError(_n.last_error(), int(nout.value), int(wout.value))
+        if rc != _n.CTOK_OK:
+            _raise(rc)
+        self.last_stats = st.as_dict()
+        return int(nout.value), int(wout.value)
 
     def encode_offsets(self, texts):
         """Per text: (ids, offsets, word_ids) of encode_single_to_encoding

@@ -99,6 +99,7 @@ CTOK_P_PAD_TO_MAX = 16
 CTOK_P_PAD_LEFT = 32
 CTOK_P_PAD_ID = 64
 CTOK_P_NO_POSTPROCESS = 128
+CTOK_P_WINDOWS = 256
 CTOK_PP_SEQUENCE = 0xFFFFFFFF
 
 
@@ -164,6 +165,11 @@ SIGS = {
                                           ctypes.POINTER(Exec), ctypes.POINTER(Stats)]),
     "ctok_encode_padded_device": (ctypes.c_int, [_p, _p, _p, _u64, _u64, ctypes.POINTER(PadOpts), _p, _p, _p, _p, _u64, _p,
                                                  _u64p, ctypes.POINTER(Exec), ctypes.POINTER(Stats)]),
+    "ctok_encode_windows": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.POINTER(PadOpts), _u64, _p, _p, _p, _p, _u64, _p, _p,
+                                           _p, _u64, _p, _u64p, _u64p, ctypes.POINTER(Exec), ctypes.POINTER(Stats)]),
+    "ctok_encode_windows_device": (ctypes.c_int, [_p, _p, _p, _u64, _u64, ctypes.POINTER(PadOpts), _u64, _p, _p, _p, _p,
+                                                  _u64, _p, _p, _p, _u64, _p, _u64p, _u64p, ctypes.POINTER(Exec),
+                                                  ctypes.POINTER(Stats)]),
     "ctok_model_max_length": (_u64, [_p]),
     "ctok_pad_id": (ctypes.c_uint32, [_p]),
     "ctok_num_special_tokens_to_add": (_u64, [_p, ctypes.c_int]),

@@ -13,6 +13,7 @@
 
 #include "host_internal.h"
 #include "knobs.h"
+#include "window_hd.h"
 
 namespace ctok_rt __attribute__((visibility("hidden"))) {
 
@@ -731,6 +732,66 @@ int ctok_encode_batch(const ctok* tc, const uint8_t* utf8_in, const uint64_t* do
   });
 }
 
+// The front of the padded and the windowed encode: the batch encoded into pad_ids / pad_tokoff,
+// the sorted special ids and the zeroed counters on the device, and the rows described in a
+// PadWork (outputs, width and row_len are the caller's to fill)
+static PadWork pad_front(ctok* t, DeviceState* ds, hipStream_t s, bool timing, const uint8_t* d_utf8,
+                         const uint64_t* d_doc_off, uint64_t n_docs, uint64_t n_bytes, const ctok_pad_opts* o,
+                         uint64_t rows, ctok_stats* st) {
+  const uint32_t f = o->flags;
+  const bool pairs = f & CTOK_P_PAIRS;
+  const bool add_special = f & CTOK_P_ADD_SPECIAL;
+  // 1. encode (encode_to_encoding flavour: no added-token split)
+  const uint64_t cap_ids = ctok_ids_bound(t, n_bytes, n_docs);
+  ds->pad_ids.ensure(cap_ids);
+  ds->pad_tokoff.ensure(n_docs + 1);
+  EncodeCall call;
+  call.text = d_utf8, call.doc_off = d_doc_off, call.n_docs = n_docs, call.n_bytes = n_bytes;
+  call.ids = ds->pad_ids.p, call.ids_cap = ds->pad_ids.cap, call.tok_off = ds->pad_tokoff.p;
+  call.stream = s, call.timing = timing, call.stats = st;
+  call.split_added = !add_special;
+  encode_device(t, ds, call);
+  // 2. row lengths and the longest row
+  std::vector<uint32_t> sp;
+  for (const auto& e : t->special) sp.push_back(e.second);
+  std::sort(sp.begin(), sp.end());
+  sp.erase(std::unique(sp.begin(), sp.end()), sp.end());
+  ds->pad_special.ensure(sp.size() + 1);
+  if (!sp.empty()) HIPTRY(hipMemcpyAsync(ds->pad_special.p, sp.data(), sp.size() * 4, hipMemcpyHostToDevice, s));
+  ds->pad_ctr.ensure(4);
+  HIPTRY(hipMemsetAsync(ds->pad_ctr.p, 0, 16, s));
+  PadWork w{};
+  w.ids = ds->pad_ids.p;
+  w.tok_off = ds->pad_tokoff.p;
+  w.n_rows = (uint32_t)rows;
+  w.pairs = pairs ? 1 : 0;
+  w.use_tpl = (add_special && t->has_pp && !(f & CTOK_P_NO_POSTPROCESS)) ? 1 : 0;
+  w.n_items = w.use_tpl ? (uint32_t)t->pp_items.size() : 0;
+  for (uint32_t k = 0; k < w.n_items; k++) w.items[k] = t->pp_items[k];
+  w.mark = (add_special && !(f & CTOK_P_NO_POSTPROCESS)) ? 1 : 0;
+  w.special_ids = ds->pad_special.p;
+  w.n_special = (uint32_t)sp.size();
+  w.truncate = (f & CTOK_P_TRUNCATE) ? 1 : 0;
+  w.max_len = o->max_length;
+  w.target = 0;
+  if (f & CTOK_P_PAD_TO_MAX) w.target = o->max_length;
+  w.pad_left = (f & CTOK_P_PAD_LEFT) ? 1 : 0;
+  w.pad_id = (f & CTOK_P_PAD_ID) ? o->pad_id : ctok_pad_id(t);
+  w.counters = ds->pad_ctr.p;
+  return w;
+}
+
+// rows of a padded call's batch, and the checks on its options that need no device
+static uint64_t pad_rows_of(const ctok* t, const ctok_pad_opts* o, uint64_t n_docs) {
+  const bool pairs = o->flags & CTOK_P_PAIRS;
+  if (pairs && (n_docs & 1)) throw_err(CTOK_E_ARG, "CTOK_P_PAIRS needs an even number of documents");
+  const uint64_t rows = pairs ? n_docs / 2 : n_docs;
+  if (rows >= 0xFFFFFFFFull) throw_err(CTOK_E_ARG, "too many rows");
+  if ((o->flags & CTOK_P_ADD_SPECIAL) && t->pp_items.size() > (size_t)kPadMaxItems)
+    throw_err(CTOK_E_UNSUPPORTED, "post-processor template with more than 16 items");
+  return rows;
+}
+
 int ctok_encode_padded_device(const ctok* tc, const uint8_t* d_utf8, const uint64_t* d_doc_off, uint64_t n_docs,
                               uint64_t n_bytes, const ctok_pad_opts* o, uint32_t* d_ids, uint32_t* d_attn,
                               uint32_t* d_type, uint32_t* d_special, uint64_t cap, uint64_t* d_row_len,
@@ -741,55 +802,13 @@ int ctok_encode_padded_device(const ctok* tc, const uint8_t* d_utf8, const uint6
   return run([&] {
     double t0 = now_ms();
     const uint32_t f = o->flags;
-    const bool pairs = f & CTOK_P_PAIRS;
-    if (pairs && (n_docs & 1)) throw_err(CTOK_E_ARG, "CTOK_P_PAIRS needs an even number of documents");
-    const uint64_t rows = pairs ? n_docs / 2 : n_docs;
-    if (rows >= 0xFFFFFFFFull) throw_err(CTOK_E_ARG, "too many rows");
-    const bool add_special = f & CTOK_P_ADD_SPECIAL;
-    if (add_special && t->pp_items.size() > (size_t)kPadMaxItems)
-      throw_err(CTOK_E_UNSUPPORTED, "post-processor template with more than 16 items");
+    const uint64_t rows = pad_rows_of(t, o, n_docs);
     DeviceCall dc(t, exec);
     DeviceState* ds = dc.ds;
     hipStream_t s = dc.s;
-    // 1. encode (encode_to_encoding flavour: no added-token split)
-    const uint64_t cap_ids = ctok_ids_bound(t, n_bytes, n_docs);
-    ds->pad_ids.ensure(cap_ids);
-    ds->pad_tokoff.ensure(n_docs + 1);
     ctok_stats st{};
-    EncodeCall call;
-    call.text = d_utf8, call.doc_off = d_doc_off, call.n_docs = n_docs, call.n_bytes = n_bytes;
-    call.ids = ds->pad_ids.p, call.ids_cap = ds->pad_ids.cap, call.tok_off = ds->pad_tokoff.p;
-    call.stream = s, call.timing = dc.timing, call.stats = &st;
-    call.split_added = !add_special;
-    encode_device(t, ds, call);
-    // 2. row lengths and the longest row
-    std::vector<uint32_t> sp;
-    for (const auto& e : t->special) sp.push_back(e.second);
-    std::sort(sp.begin(), sp.end());
-    sp.erase(std::unique(sp.begin(), sp.end()), sp.end());
-    ds->pad_special.ensure(sp.size() + 1);
-    if (!sp.empty()) HIPTRY(hipMemcpyAsync(ds->pad_special.p, sp.data(), sp.size() * 4, hipMemcpyHostToDevice, s));
-    ds->pad_ctr.ensure(4);
-    HIPTRY(hipMemsetAsync(ds->pad_ctr.p, 0, 16, s));
-    PadWork w{};
-    w.ids = ds->pad_ids.p;
-    w.tok_off = ds->pad_tokoff.p;
-    w.n_rows = (uint32_t)rows;
-    w.pairs = pairs ? 1 : 0;
-    w.use_tpl = (add_special && t->has_pp && !(f & CTOK_P_NO_POSTPROCESS)) ? 1 : 0;
-    w.n_items = w.use_tpl ? (uint32_t)t->pp_items.size() : 0;
-    for (uint32_t k = 0; k < w.n_items; k++) w.items[k] = t->pp_items[k];
-    w.mark = (add_special && !(f & CTOK_P_NO_POSTPROCESS)) ? 1 : 0;
-    w.special_ids = ds->pad_special.p;
-    w.n_special = (uint32_t)sp.size();
-    w.truncate = (f & CTOK_P_TRUNCATE) ? 1 : 0;
-    w.max_len = o->max_length;
-    w.target = 0;
-    if (f & CTOK_P_PAD_TO_MAX) w.target = o->max_length;
-    w.pad_left = (f & CTOK_P_PAD_LEFT) ? 1 : 0;
-    w.pad_id = (f & CTOK_P_PAD_ID) ? o->pad_id : ctok_pad_id(t);
+    PadWork w = pad_front(t, ds, s, dc.timing, d_utf8, d_doc_off, n_docs, n_bytes, o, rows, &st);
     w.row_len = d_row_len;
-    w.counters = ds->pad_ctr.p;
     HIPTRY(launch_pad_len(w, s));
     HIPTRY(hipMemcpyAsync(ds->host + kPinScratch, ds->pad_ctr.p, 16, hipMemcpyDeviceToHost, s));
     spin_sync(ds, s);
@@ -858,6 +877,150 @@ int ctok_encode_padded(const ctok* tc, const uint8_t* utf8, const uint64_t* doc_
     }
     HIPTRY(hipStreamSynchronize(s));
     if (rc == CTOK_E_CAPACITY) throw_err(CTOK_E_CAPACITY, "cap too small: *width_out holds the row width needed");
+  });
+}
+
+// The window calls' checks that need no device: the reference's loop never ends with stride >= max_length
+static void check_window_opts(const ctok_pad_opts* o, uint64_t stride) {
+  if (!win::valid(o->max_length, stride))
+    throw_err(CTOK_E_ARG, "stride must be smaller than max_length (the reference's truncate_with_stride never ends)");
+}
+
+static const char* const kWinCapacityMsg =
+    "cap or win_cap too small: *n_windows_out and *width_out hold the windows and the row width needed";
+
+// Overflowing stride windows (Encoding::truncate_with_stride, src/encoding.rs:175-223): the padded
+// encode's rows, each cut into its windows on the device (pad.hip k_win_len, scan, k_win_rows).
+int ctok_encode_windows_device(const ctok* tc, const uint8_t* d_utf8, const uint64_t* d_doc_off, uint64_t n_docs,
+                               uint64_t n_bytes, const ctok_pad_opts* o, uint64_t stride, uint32_t* d_ids,
+                               uint32_t* d_attn, uint32_t* d_type, uint32_t* d_special, uint64_t cap,
+                               uint64_t* d_win_len, uint32_t* d_win_row, uint64_t* d_win_start, uint64_t win_cap,
+                               uint64_t* d_row_win, uint64_t* n_windows_out, uint64_t* width_out,
+                               const ctok_exec* exec, ctok_stats* stats) {
+  if (!tc || !o || !d_doc_off || !d_row_win || !n_windows_out || !width_out || (n_bytes && !d_utf8))
+    return fail(CTOK_E_ARG, "null argument");
+  ctok* t = const_cast<ctok*>(tc);
+  return run([&] {
+    double t0 = now_ms();
+    check_window_opts(o, stride);
+    ctok_pad_opts po = *o;
+    po.flags |= CTOK_P_TRUNCATE | CTOK_P_WINDOWS;
+    const uint32_t f = po.flags;
+    const uint64_t rows = pad_rows_of(t, &po, n_docs);
+    DeviceCall dc(t, exec);
+    DeviceState* ds = dc.ds;
+    hipStream_t s = dc.s;
+    ctok_stats st{};
+    WinWork w{};
+    w.p = pad_front(t, ds, s, dc.timing, d_utf8, d_doc_off, n_docs, n_bytes, &po, rows, &st);
+    w.stride = stride;
+    w.row_win = d_row_win;
+    // Encoding::from_ids rows: added-token ids without a vocab string leave `tokens` short (k_win_tokens)
+    std::vector<uint32_t> tokenless;
+    if (!(f & CTOK_P_ADD_SPECIAL))
+      for (uint32_t id : t->at_id)
+        if (!t->id_to_token.count(id)) tokenless.push_back(id);
+    std::sort(tokenless.begin(), tokenless.end());
+    tokenless.erase(std::unique(tokenless.begin(), tokenless.end()), tokenless.end());
+    if (!tokenless.empty()) {
+      ds->win_tokenless.ensure(tokenless.size());
+      HIPTRY(hipMemcpyAsync(ds->win_tokenless.p, tokenless.data(), tokenless.size() * 4, hipMemcpyHostToDevice, s));
+      w.tokenless = ds->win_tokenless.p;
+      w.n_tokenless = (uint32_t)tokenless.size();
+      w.ids_bound = ctok_ids_bound(t, n_bytes, n_docs);
+    }
+    // windows per row, scanned into each row's first window; the total at [rows]
+    HIPTRY(launch_win_len(w, s));
+    ds->scan_tmp.ensure(scan_tmp_elems(rows + 1) + 64);
+    HIPTRY(scan_u64(d_row_win, rows, ds->scan_tmp.p, ds->scan_tmp.cap, s));
+    // one readback: the longest main window and the flags, then the total
+    HIPTRY(hipMemcpyAsync(ds->host + kPinScratch, ds->pad_ctr.p, 16, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(ds->host + kPinScratch + 2, d_row_win + rows, 8, hipMemcpyDeviceToHost, s));
+    spin_sync(ds, s);
+    const uint64_t longest = pinned<uint64_t>(ds, kPinScratch)[0];
+    const uint32_t dropped = pinned<uint32_t>(ds, kPinScratch)[2];
+    const uint32_t unsliceable = pinned<uint32_t>(ds, kPinScratch)[3];
+    const uint64_t n_windows = pinned<uint64_t>(ds, kPinScratch)[2];
+    if (w.p.use_tpl && dropped)
+      throw_err(CTOK_E_PANIC, "attempt to subtract with overflow: the post-processor template drops ids (reference src/huggingface/mod.rs:378)");
+    if (unsliceable)
+      throw_err(CTOK_E_PANIC, "range end index out of range for slice: a row longer than max_length has fewer tokens than ids -- the post-processor does not extend `tokens`, and without special tokens ids that have no vocab string are left out (reference src/encoding.rs:189)");
+    if (n_windows >= 0xFFFFFFFFull) throw_err(CTOK_E_ARG, "too many windows (the call is limited to < 2^32); split the batch");
+    // padding as Tokenizer.__call__: window 0 of each row to the longest main window or to max_length
+    if ((f & CTOK_P_PAD_LONGEST) && !(f & CTOK_P_PAD_TO_MAX)) w.p.target = longest;
+    const uint64_t width = std::max<uint64_t>(longest, w.p.target);
+    *n_windows_out = n_windows;
+    *width_out = width;
+    w.n_windows = n_windows;
+    w.p.width = width;
+    if (n_windows > win_cap || (width && n_windows > cap / width)) throw_err(CTOK_E_CAPACITY, kWinCapacityMsg);
+    if (n_windows && (!d_win_len || !d_win_row)) throw_err(CTOK_E_ARG, "null window records");
+    if (n_windows * width && !d_ids) throw_err(CTOK_E_ARG, "null ids");
+    w.p.out_ids = d_ids;
+    w.p.out_attn = d_attn;
+    w.p.out_type = d_type;
+    w.p.out_special = d_special;
+    w.win_len = d_win_len;
+    w.win_row = d_win_row;
+    w.win_start = d_win_start;
+    HIPTRY(launch_win_rows(w, s));
+    spin_sync(ds, s);
+    if (stats) {
+      *stats = st;
+      stats->ms_total = now_ms() - t0;
+    }
+  });
+}
+
+int ctok_encode_windows(const ctok* tc, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs,
+                        const ctok_pad_opts* o, uint64_t stride, uint32_t* ids, uint32_t* attn, uint32_t* type,
+                        uint32_t* special, uint64_t cap, uint64_t* win_len, uint32_t* win_row, uint64_t* win_start,
+                        uint64_t win_cap, uint64_t* row_win, uint64_t* n_windows_out, uint64_t* width_out,
+                        const ctok_exec* exec, ctok_stats* stats) {
+  if (!tc || !o || !doc_off || !row_win || !n_windows_out || !width_out) return fail(CTOK_E_ARG, "null argument");
+  ctok* t = const_cast<ctok*>(tc);
+  return run([&] {
+    check_window_opts(o, stride);
+    check_host_batch(utf8, doc_off, n_docs, "doc_off");
+    const uint64_t B = doc_off[n_docs];
+    const uint64_t rows = (o->flags & CTOK_P_PAIRS) ? n_docs / 2 : n_docs;
+    // held from staging to readback, as in ctok_encode_padded
+    DeviceCall dc(t, exec);
+    DeviceState* ds = dc.ds;
+    hipStream_t s = dc.s;
+    ds->win_rowwin.ensure(rows + 1);
+    for (auto& b : ds->pad_out) b.ensure(cap ? cap : 1);
+    ds->win_len.ensure(win_cap ? win_cap : 1);
+    ds->win_row.ensure(win_cap ? win_cap : 1);
+    ds->win_start.ensure(win_cap ? win_cap : 1);
+    stage_host_batch(ds, utf8, doc_off, n_docs, s);
+    ctok_exec ex = exec ? *exec : ctok_exec{};
+    ex.stream = s;
+    uint64_t n_windows = 0, width = 0;
+    const int rc = ctok_encode_windows_device(
+        t, ds->pad_in_text.p, ds->pad_in_off.p, n_docs, B, o, stride, ds->pad_out[0].p, attn ? ds->pad_out[1].p : nullptr,
+        type ? ds->pad_out[2].p : nullptr, special ? ds->pad_out[3].p : nullptr, cap, ds->win_len.p, ds->win_row.p,
+        win_start ? ds->win_start.p : nullptr, win_cap, ds->win_rowwin.p, &n_windows, &width, &ex, stats);
+    *n_windows_out = n_windows;
+    *width_out = width;
+    if (rc != CTOK_OK && rc != CTOK_E_CAPACITY) throw_err(rc, g_err);
+    HIPTRY(hipMemcpyAsync(row_win, ds->win_rowwin.p, (rows + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (rc == CTOK_OK && n_windows) {
+      if (!win_len || !win_row) throw_err(CTOK_E_ARG, "null window records");
+      HIPTRY(hipMemcpyAsync(win_len, ds->win_len.p, n_windows * 8, hipMemcpyDeviceToHost, s));
+      HIPTRY(hipMemcpyAsync(win_row, ds->win_row.p, n_windows * 4, hipMemcpyDeviceToHost, s));
+      if (win_start) HIPTRY(hipMemcpyAsync(win_start, ds->win_start.p, n_windows * 8, hipMemcpyDeviceToHost, s));
+    }
+    if (rc == CTOK_OK && n_windows * width) {
+      if (!ids) throw_err(CTOK_E_ARG, "null ids");
+      const size_t nb = n_windows * width * 4;
+      HIPTRY(hipMemcpyAsync(ids, ds->pad_out[0].p, nb, hipMemcpyDeviceToHost, s));
+      if (attn) HIPTRY(hipMemcpyAsync(attn, ds->pad_out[1].p, nb, hipMemcpyDeviceToHost, s));
+      if (type) HIPTRY(hipMemcpyAsync(type, ds->pad_out[2].p, nb, hipMemcpyDeviceToHost, s));
+      if (special) HIPTRY(hipMemcpyAsync(special, ds->pad_out[3].p, nb, hipMemcpyDeviceToHost, s));
+    }
+    HIPTRY(hipStreamSynchronize(s));
+    if (rc == CTOK_E_CAPACITY) throw_err(CTOK_E_CAPACITY, kWinCapacityMsg);
   });
 }
 

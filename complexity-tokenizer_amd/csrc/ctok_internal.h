@@ -389,10 +389,33 @@ struct PadWork {
   uint32_t* out_type;
   uint32_t* out_special;
   uint64_t* row_len;         // [n_rows] length of the row (content + padding)
-  uint32_t* counters;        // [0..1] longest content (u64, atomicMax), [2] a template dropped ids
+  uint32_t* counters;        // [0..1] longest content (u64, atomicMax), [2] a template dropped ids,
+                             // [3] windows only: an overflowing row with fewer tokens than ids
 };
 hipError_t launch_pad_len(const PadWork& w, hipStream_t s);
 hipError_t launch_pad_rows(const PadWork& w, hipStream_t s);
+
+// Overflowing stride windows (window_hd.h; Encoding::truncate_with_stride, src/encoding.rs:175-223):
+// a row longer than max_len becomes 1 + ceil((P - max_len) / (max_len - stride)) windows of the
+// outputs instead of one cut row.  p is the padded encode's work with truncate = 1 (its L is then
+// the main window's length); p.width, p.out_* describe [n_windows, width] arrays and p.row_len is
+// unused.  counters[3]: a row overflows and has fewer tokens than ids -- the reference slices
+// `tokens` past its end (src/encoding.rs:189): the post-processor does not extend it, and
+// Encoding::from_ids leaves out the ids that have no vocab string.
+struct WinWork {
+  PadWork p;
+  uint64_t stride;           // < p.max_len
+  const uint32_t* tokenless; // sorted ids encode can emit that have no vocab string (from_ids rows; else n = 0)
+  uint32_t n_tokenless;
+  uint64_t ids_bound;        // at least the batch's ids (k_win_tokens' grid)
+  uint64_t* row_win;         // [n_rows + 1] k_win_len: windows of the row; scanned: its first window
+  uint64_t n_windows;        // row_win[n_rows] after the scan
+  uint64_t* win_len;         // [n_windows] length of the window's Encoding (window 0: content + padding)
+  uint32_t* win_row;         // [n_windows] its row (overflow_to_sample_mapping)
+  uint64_t* win_start;       // [n_windows] its first content position, k * (max_len - stride); may be null
+};
+hipError_t launch_win_len(const WinWork& w, hipStream_t s);
+hipError_t launch_win_rows(const WinWork& w, hipStream_t s);
 
 // ---- launchers (kernels.hip) -----------------------------------------------------------
 void upload_done();

@@ -152,14 +152,14 @@ constexpr size_t kPinFinal = 1;     // the final counters (k_tokoff, or copied):
 constexpr size_t kPinReport = 64;   // the report (k_report / k_bpe_short): kNumCounters u32, then the sequence number
 constexpr size_t kPinLongTot = 96;  // the long pieces' totals: ids, global-memory state words (2 u32)
 constexpr size_t kPinSplice = 100;  // nfc_splice: sub-batch bytes, flagged docs (2 u64)
-constexpr size_t kPinScratch = 102; // any other small readback between syncs (2 u64): NFC doc count,
-                                    // normalised size, the decode and pad counters
+constexpr size_t kPinScratch = 102; // any other small readback between syncs (3 u64): NFC doc count,
+                                    // normalised size, the decode and pad counters, the window total
 static_assert(kPinFinal == kPinNtok + 1, "k_tokoff writes the counters right after the token count");
 static_assert(kPinFinal * 8 + kNumCounters * 4 <= kPinReport * 8, "final counters run into the report");
 static_assert(kPinReport * 8 + (kNumCounters + 1) * 4 <= kPinLongTot * 8, "report runs into the long totals");
 static_assert(kPinLongTot * 8 + 2 * 4 <= kPinSplice * 8, "long totals run into the splice words");
 static_assert(kPinSplice + 2 <= kPinScratch, "splice words run into the scratch slot");
-static_assert((kPinScratch + 2) * 8 <= kPinBytes, "pinned words outgrow their block");
+static_assert((kPinScratch + 3) * 8 <= kPinBytes, "pinned words outgrow their block");
 
 struct DeviceState {
   int device = -1;
@@ -223,6 +223,9 @@ struct DeviceState {
   // padded encode: encoded ids, special ids, counters; host-API input / outputs
   DevBuf<uint32_t> pad_ids, pad_special, pad_ctr, pad_out[4];
   DevBuf<uint64_t> pad_tokoff, pad_rowlen, pad_in_off;
+  // its overflowing windows (ctok_encode_windows): per-window records, per-row first windows
+  DevBuf<uint64_t> win_len, win_start, win_rowwin;
+  DevBuf<uint32_t> win_row, win_tokenless;
   DevBuf<uint8_t> pad_in_text;
   // bytes of device memory held for encode calls (the workspace, not the tokenizer tables)
   uint64_t workspace_bytes() const {

@@ -282,6 +282,54 @@ int ctok_encode_padded_device(const ctok* tok, const uint8_t* d_utf8, const uint
                               uint64_t n_bytes, const ctok_pad_opts* opts, uint32_t* d_ids, uint32_t* d_attention,
                               uint32_t* d_type_ids, uint32_t* d_special, uint64_t cap, uint64_t* d_row_len,
                               uint64_t* width_out, const ctok_exec* exec, ctok_stats* stats);
+
+/* ------------------------------------------------- overflowing stride windows of the padded encode
+ * Encoding::truncate_with_stride (src/encoding.rs:175-223; Tokenizer.__call__(truncation=True,
+ * stride > 0), src/bindings/tokenizer.rs:102-112, and encode_with_truncation, src/huggingface/
+ * mod.rs:348-392) on the GPU: a row is encoded and post-processed as by ctok_encode_padded, and one
+ * longer than m = opts->max_length becomes 1 + ceil((P - m) / (m - stride)) windows instead of one
+ * cut row (P: its processed length).  Window k of a row holds its content positions
+ * [k * (m - stride), min(k * (m - stride) + m, P)); window 0 is the truncated main encoding, the
+ * others its `overflowing` list in order.  A row of P <= m is one window.  stride = 0 gives plain
+ * consecutive windows (encode_with_truncation's stride 0, not the single remainder of
+ * Encoding::truncate).  opts->flags as for ctok_encode_padded; these two calls imply
+ * CTOK_P_TRUNCATE | CTOK_P_WINDOWS (the flag names the mode in a ctok_pad_opts that travels with
+ * its results; ctok_encode_padded itself has no windows and ignores it).
+ *   - The outputs are [n_windows, width] arrays, the windows of row r at
+ *     row_win[r] .. row_win[r + 1] (row_win: [rows + 1], row_win[rows] = n_windows).  Window w
+ *     occupies ids[w*width .. w*width + win_len[w]); win_row[w] is its row (the
+ *     overflow_to_sample_mapping) and win_start[w] its first content position.
+ *   - Padding as Tokenizer.__call__: to the longest main window (CTOK_P_PAD_LONGEST) or to m
+ *     (CTOK_P_PAD_TO_MAX), window 0 of each row only (on the left with CTOK_P_PAD_LEFT); the
+ *     overflowing windows keep their slice length.  Cells at or past win_len[w] hold padding
+ *     values.  width = max(longest window, padding target).
+ *   - stride >= max_length (max_length 0 included) never ends in the reference: CTOK_E_ARG,
+ *     checked before any device is used.
+ *   - The reference slices `tokens` up to P (src/encoding.rs:189), and a row can have fewer tokens
+ *     than ids: the post-processor does not extend `tokens`, and without CTOK_P_ADD_SPECIAL
+ *     (Encoding::from_ids) ids that have no model.vocab string -- added tokens with ids of their own
+ *     -- are left out of it.  Such a row panics when it overflows: CTOK_E_PANIC.  So windows have
+ *     values where the post-processor adds nothing (none, CTOK_P_NO_POSTPROCESS, no
+ *     CTOK_P_ADD_SPECIAL) and, without CTOK_P_ADD_SPECIAL, the overflowing rows hold vocab ids only;
+ *     otherwise only while no row overflows.
+ *   - attention / type_ids / special_mask / win_start may be NULL.  cap = cells available in each
+ *     array, win_cap = entries in win_len / win_row / win_start.  n_windows > win_cap or
+ *     n_windows * width > cap -> CTOK_E_CAPACITY with *n_windows_out, *width_out and row_win
+ *     filled and nothing else written.  n_windows must stay below 2^32 (CTOK_E_ARG). */
+#define CTOK_P_WINDOWS 256u
+int ctok_encode_windows(const ctok* tok, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs,
+                        const ctok_pad_opts* opts, uint64_t stride, uint32_t* ids, uint32_t* attention_mask,
+                        uint32_t* type_ids, uint32_t* special_mask, uint64_t cap, uint64_t* win_len,
+                        uint32_t* win_row, uint64_t* win_start, uint64_t win_cap, uint64_t* row_win,
+                        uint64_t* n_windows_out, uint64_t* width_out, const ctok_exec* exec, ctok_stats* stats);
+/* Same on HBM-resident buffers (device pointers, work on exec->stream); n_bytes = doc_off[n_docs]. */
+int ctok_encode_windows_device(const ctok* tok, const uint8_t* d_utf8, const uint64_t* d_doc_off, uint64_t n_docs,
+                               uint64_t n_bytes, const ctok_pad_opts* opts, uint64_t stride, uint32_t* d_ids,
+                               uint32_t* d_attention, uint32_t* d_type_ids, uint32_t* d_special, uint64_t cap,
+                               uint64_t* d_win_len, uint32_t* d_win_row, uint64_t* d_win_start, uint64_t win_cap,
+                               uint64_t* d_row_win, uint64_t* n_windows_out, uint64_t* width_out,
+                               const ctok_exec* exec, ctok_stats* stats);
+
 /* The model_max_length used when max_length is not given (512 for from_file / from_str,
  * src/huggingface/mod.rs:243-245) and the pad id the reference picks (mod.rs:500-504). */
 uint64_t ctok_model_max_length(const ctok* tok);
