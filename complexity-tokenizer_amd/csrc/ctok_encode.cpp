@@ -493,6 +493,7 @@ void size_workspace(Enc& e, Attempt& a) {
   w.nfc_watch = a.speculate ? (e.splice ? 2u : 1u) : 0u;
   w.keep_first = e.c.mode == EncodeMode::KeepFirst ? 1u : 0u;
   w.short_wgs = e.knobs.short_wgs;
+  w.chunk_sort = e.knobs.chunk_sort;
   const size_t nt = w.n_tiles;
   a.cap = plan_capacities(a.B, nt, a.safe, e.tb.n_at, pk.unit, e.knobs.c3_sparse);
   w.k0 = a.cap.k0;

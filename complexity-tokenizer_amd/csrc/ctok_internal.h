@@ -262,6 +262,7 @@ struct Work {              // device pointers, sized by the host for one call
                            // NFC might change (zeroed by the host; nfc_splice flags docs from it)
   uint32_t mid_wide;       // 1: the 17..32 B pass at 768 threads per workgroup (the call has no long pieces)
   uint32_t short_wgs;      // workgroups of k_bpe_short (0: one per CU)
+  uint32_t chunk_sort;     // how the <= 32 B merge passes order a chunk's pieces (chunk_sort_hd.h, CTOK_CHUNK_SORT)
   uint32_t keep_first;     // 1: k_emit leaves every piece's first id within its tile in tcnt (not
                            // only doc-start pieces'), for ctok_encode_offsets
   uint16_t* wpref;         // [n_tiles * 64] pieces of the tile before each 64-byte word

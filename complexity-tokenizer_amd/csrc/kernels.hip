@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "ctok_internal.h"
+#include "chunk_sort_hd.h"
 #include "merge_packed_hd.h"
 #include "seg_lane.h"
 
@@ -1513,9 +1514,65 @@ __device__ __forceinline__ void defer_to_generic(const Work& w, uint32_t s, uint
 // (KT: the most tiles per chunk of the passes that share it)
 template <uint32_t SORTCAP, int KT = 64>
 struct PassLds {
-  uint32_t pre[KT + 1], tsum[KT], tbase[KT], stat[2], bcnt[4], bfill[4], chunk, take, next;
-  uint16_t perm[SORTCAP];  // the chunk's entries ordered by length bucket
+  uint32_t pre[KT + 1], tsum[KT], tbase[KT], stat[2], bcnt[csort::kMaxBuckets], bfill[csort::kMaxBuckets], chunk, take, next;
+  uint16_t perm[SORTCAP];  // the chunk's first SORTCAP entries ordered by length bucket
 };
+
+// Counting sort of the chunk's first Es <= SORTCAP list entries by csort::code (chunk_sort_hd.h)
+// into S.perm; the order within a bucket is free.  Each entry is read once: thread tid owns
+// entries tid, tid + NT, ... (unrolled in groups of four whose tile bisections and list loads are
+// all in flight together) and takes its rank within the bucket from one returning
+// add on the bucket's workgroup counter (ds_add_rtn_u32; S.bcnt, zero on entry), keeps code and
+// rank packed in a register, and after the counters' scan by the first wave stores the entry
+// number at base + rank.  (Counters per wave would not be faster -- the LDS serialises the lanes of
+// one instruction that hit one address, not the waves -- and would cost 1 KiB of the sort buffer;
+// a ballot per bucket costs its instructions once per bucket, 8 or 16 here.)
+template <int N, int K, uint32_t NT, uint32_t SORTCAP, class PL>
+__device__ __forceinline__ void chunk_sort(PL& S, const uint32_t* list, uint32_t c0, uint32_t cap, uint32_t Es,
+                                           uint32_t mode) {
+  static_assert(SORTCAP <= 65536, "perm holds u16 entry numbers, a rank fits 16 bits");
+  constexpr uint32_t G = 4, EPT = (SORTCAP + G * NT - 1) / (G * NT) * G;  // entries per thread, whole groups
+  uint32_t tid = threadIdx.x;
+  // (opaque: what is derived from it is computed here, per chunk, instead of being hoisted out of
+  // the chunk loop and held in registers through the piece loop, which has none to spare)
+  asm volatile("" : "+v"(tid));
+  uint32_t cr[EPT];  // code << 16 | rank (compile-time indices only)
+#pragma unroll
+  for (uint32_t j = 0; j < EPT; j++) cr[j] = 0;
+#pragma unroll
+  for (uint32_t g = 0; g < EPT; g += G) {
+    if (g * NT < Es) {  // workgroup-uniform
+      uint32_t e[G];
+#pragma unroll
+      for (uint32_t j = 0; j < G; j++) {
+        // (no branch: the group's bisections interleave; a thread past the end reads the last entry)
+        const uint32_t q = min(tid + (g + j) * NT, Es - 1);
+        const uint32_t kt = tile_of<K>(S.pre, q);
+        e[j] = list[(size_t)(c0 + kt) * cap + (q - S.pre[kt])];
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < G; j++) {
+        if (tid + (g + j) * NT < Es) {
+          const uint32_t c = csort::code(N, mode, ent_len(e[j]));
+          cr[g + j] = (c << 16) | atomicAdd(&S.bcnt[c], 1u);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < 64) {  // exclusive scan of the bucket sizes
+    const uint32_t c = tid < csort::kMaxBuckets ? S.bcnt[tid] : 0u;
+    const uint32_t inc = wave_incl_scan(c);
+    if (tid < csort::kMaxBuckets) S.bfill[tid] = inc - c;
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t j = 0; j < EPT; j++) {
+    const uint32_t q = tid + j * NT;
+    if (q < Es) S.perm[S.bfill[cr[j] >> 16] + (cr[j] & 0xFFFFu)] = (uint16_t)q;
+  }
+  __syncthreads();
+}
 
 // Merge pass over one length class (N = 8, 16, 32 slots), run by a persistent grid:
 // workgroups take chunks of w.unit-tile units from a counter (up to KT / w.unit units at once when the
@@ -1547,10 +1604,13 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
   const uint32_t* counts = w.tcls + (size_t)LC::cls * w.n_tiles;
   uint32_t st_bytes = 0, st_ids = 0;
   if (tid < 2) S.stat[tid] = 0;
-  // length buckets (4 per class): a wavefront's pieces then have similar lengths, hence
-  // similar merge counts, and fewer of its lanes idle while the longest piece finishes
-  constexpr uint32_t blo = N == 8 ? 1 : N / 2 + 1, bw = N == 64 ? 8 : N == 32 ? 4 : 2;
-  auto bucket = [&](uint32_t n) { return min(3u, (n - blo) / bw); };
+  // The chunk's entries are walked by length bucket (chunk_sort_hd.h: exact byte lengths in the
+  // 9..16 B and 17..32 B passes): a wavefront's pieces then have the same trip counts in the tiers,
+  // and few of its lanes idle while the longest piece finishes.  Longest bucket first, so that the
+  // short merge chains are the ones at the chunk's barrier (shortest first: +0.08 ms on C4).
+  // (Work::chunk_sort selects the A/B arms; it is a kernel argument, read per chunk outside the
+  // piece loop.)
+  const uint32_t mode = w.chunk_sort;
   // chunks of K tiles dealt dynamically (one atomic per chunk, taken by thread 0 and broadcast
   // through LDS): workgroups that start late, or whose CU is shared, take fewer chunks
   __syncthreads();
@@ -1562,6 +1622,7 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
       S.take = take;
       S.next = 0;
     }
+    if (tid < csort::kMaxBuckets) S.bcnt[tid] = 0;  // (chunk_sort's counters)
     __syncthreads();
     const uint32_t c0 = S.chunk * U;
     if (c0 >= w.n_tiles) break;
@@ -1572,42 +1633,57 @@ __device__ __forceinline__ void class_pass(const Work& w, const Tables& t, const
       loaded = true;
       __syncthreads();
     }
-    const bool sorted = N > 8 && E <= SORTCAP;  // <= 8 B pieces: few merges, sorting does not pay
-    if (sorted) {
-      if (tid < 4) { S.bcnt[tid] = 0; S.bfill[tid] = 0; }
-      __syncthreads();
-      for (uint32_t q = tid; q < E; q += NT) {  // bucket sizes (one LDS add per wave and bucket)
-        const uint32_t kt = tile_of<K>(S.pre, q);
-        const uint32_t b = bucket(ent_len(list[(size_t)(c0 + kt) * cap + (q - S.pre[kt])]));
+    // The first Es entries are walked in S.perm's order, the rest in list order after them: a
+    // dense chunk a little over SORTCAP keeps its order for all but the tail.  Unsorted (Es = 0)
+    // is the <= 8 B pass, by default: its exact order removes 13 % of the pass's VALU instructions
+    // on C4 (the model: lane use in merge_lds8_run 0.77 -> 0.96) but none of its time -- its waves
+    // wait more instead -- and costs the sort: k_bpe_short 3.41 -> 3.43 ms
+    // (profiles/chunk_sort/ab_summary.txt).
+    uint32_t Es = 0;
+    if constexpr (N > 32) {
+      // 33..64 B: four buckets of width 8 by the two-read sort, all or nothing (untouched: no
+      // English-like corpus has such a pass to measure it on)
+      if (E <= SORTCAP) {
+        Es = uni(E);
+        auto bucket = [&](uint32_t n) { return csort::bucket(N, false, n); };
+        if (tid < 4) { S.bcnt[tid] = 0; S.bfill[tid] = 0; }
+        __syncthreads();
+        for (uint32_t q = tid; q < E; q += NT) {  // bucket sizes (one LDS add per wave and bucket)
+          const uint32_t kt = tile_of<K>(S.pre, q);
+          const uint32_t b = bucket(ent_len(list[(size_t)(c0 + kt) * cap + (q - S.pre[kt])]));
 #pragma unroll
-        for (uint32_t bb = 0; bb < 4; bb++) {
-          const uint64_t m = __ballot(b == bb);
-          if (m && (threadIdx.x & 63) == __ffsll((unsigned long long)m) - 1) atomicAdd(&S.bcnt[bb], (uint32_t)__popcll(m));
+          for (uint32_t bb = 0; bb < 4; bb++) {
+            const uint64_t m = __ballot(b == bb);
+            if (m && (threadIdx.x & 63) == __ffsll((unsigned long long)m) - 1) atomicAdd(&S.bcnt[bb], (uint32_t)__popcll(m));
+          }
         }
-      }
-      __syncthreads();
-      if (tid == 0) {
-        uint32_t acc = 0;
-        for (int bb = 0; bb < 4; bb++) {
-          const uint32_t c = S.bcnt[bb];
-          S.bfill[bb] = acc;
-          acc += c;
+        __syncthreads();
+        if (tid == 0) {
+          uint32_t acc = 0;
+          for (int bb = 0; bb < 4; bb++) {
+            const uint32_t c = S.bcnt[bb];
+            S.bfill[bb] = acc;
+            acc += c;
+          }
         }
-      }
-      __syncthreads();
-      for (uint32_t q = tid; q < E; q += NT) {  // scatter entry numbers into bucket order
-        const uint32_t kt = tile_of<K>(S.pre, q);
-        const uint32_t b = bucket(ent_len(list[(size_t)(c0 + kt) * cap + (q - S.pre[kt])]));
+        __syncthreads();
+        for (uint32_t q = tid; q < E; q += NT) {  // scatter entry numbers into bucket order
+          const uint32_t kt = tile_of<K>(S.pre, q);
+          const uint32_t b = bucket(ent_len(list[(size_t)(c0 + kt) * cap + (q - S.pre[kt])]));
 #pragma unroll
-        for (uint32_t bb = 0; bb < 4; bb++) {
-          const uint32_t slot = wave_append(&S.bfill[bb], b == bb);
-          if (b == bb) S.perm[slot] = (uint16_t)q;
+          for (uint32_t bb = 0; bb < 4; bb++) {
+            const uint32_t slot = wave_append(&S.bfill[bb], b == bb);
+            if (b == bb) S.perm[slot] = (uint16_t)q;
+          }
         }
+        __syncthreads();
       }
-      __syncthreads();
+    } else if (csort::sorts(N, mode)) {
+      Es = uni(min(E, SORTCAP));  // (a scalar, as E is workgroup-uniform: it lives through the piece loop)
+      chunk_sort<N, K, NT, SORTCAP>(S, list, c0, cap, Es, mode);
     }
     auto entry = [&](uint32_t i, uint32_t& kt) {
-      const uint32_t q = sorted ? (uint32_t)S.perm[i] : i;
+      const uint32_t q = i < Es ? (uint32_t)S.perm[i] : i;
       kt = tile_of<K>(S.pre, q);
       return list[(size_t)(c0 + kt) * cap + (q - S.pre[kt])];
     };

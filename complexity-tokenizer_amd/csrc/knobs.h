@@ -6,6 +6,7 @@
 #include <optional>
 
 #include "ctok_internal.h"
+#include "chunk_sort_hd.h"
 
 namespace ctok_rt __attribute__((visibility("hidden"))) {
 
@@ -64,6 +65,8 @@ struct CallKnobs {
   bool no_nfc_speculation = env_set("CTOK_NO_NFC_SPECULATION");
   bool nfc_rerun = env_set("CTOK_NFC_RERUN");
   uint32_t short_wgs = (uint32_t)env_int("CTOK_SHORT_WGS", 0);
+  // the merge passes' chunk order, the A/B arms of chunk_sort_hd.h (per call: the tests run every value in one process)
+  uint32_t chunk_sort = (uint32_t)env_int("CTOK_CHUNK_SORT", (int)csort::kModeDefault) & csort::kModeMask;
   std::optional<uint64_t> c3_sparse = env_u64("CTOK_C3_SPARSE");  // the sparse class-3 bound (unset: the default rule)
   bool mid512 = env_set("CTOK_MID512");
   int overlap = env_int("CTOK_OVERLAP", ctok_dev::kOverlapDefault);  // >= 1: merge passes on the idle side stream
