@@ -264,7 +264,7 @@ struct HostProf {
   }
 };
 
-// CTOK_WGREC=1 (kernels.hip WgRec), per kernel: workgroups, distinct CUs, start / end spread (us from the first start)
+// CTOK_WGREC=1 (dev_common.h WgRec), per kernel: workgroups, distinct CUs, start / end spread (us from the first start)
 void print_wgrec(const uint64_t* d_wgrec) {
   std::vector<uint64_t> r(kWgRecWords);
   HIPTRY(hipMemcpy(r.data(), d_wgrec, kWgRecWords * 8, hipMemcpyDeviceToHost));
@@ -548,7 +548,7 @@ void size_workspace(Enc& e, Attempt& a) {
   // (range-checking build: every merged record starts out of range, so one no pass wrote traps)
   HIPTRY(hipMemsetAsync(ds->mrec.p, 0xFF, (size_t)nt * kTileSlots * 4, s));
 #endif
-  if (pk.wgrec) {  // diagnostic: per-workgroup records of the merge passes (kernels.hip WgRec)
+  if (pk.wgrec) {  // diagnostic: per-workgroup records of the merge passes (dev_common.h WgRec)
     bind(ds->wgrec, kWgRecWords, w.wgrec);
     HIPTRY(hipMemsetAsync(ds->wgrec.p, 0, kWgRecWords * 8, s));
   }

@@ -1,5 +1,6 @@
 // Internal interfaces between the C++ host runtime (ctok_encode.cpp, ctok_host.cpp) and the HIP
-// kernels (kernels.hip).  Not part of the C ABI.
+// kernels (the encode path by stage: segment.hip, kernels.hip, long.hip, emit.hip, scan.hip, nfc.hip;
+// decode.hip, pad.hip).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -198,7 +199,7 @@ struct Tables {            // device pointers, owned by the host runtime
   const uint8_t* nfc_s1;
   const uint16_t* nfc_s2;
   const uint8_t* cls_bmp;  // [32768] BMP code point c: nibble c & 1 of byte c >> 1 = class | NFC flag << 2
-  uint32_t cp_fast;        // 1: the code point ranges of cp_range_class (kernels.hip) hold the class
+  uint32_t cp_fast;        // 1: the code point ranges of cp_range_class (segment.hip) hold the class
                            // it gives and no NFC flag in these tables (checked at upload)
   const uint32_t* decomp_cp;
   const uint16_t* decomp_off;
@@ -223,7 +224,7 @@ struct Tables {            // device pointers, owned by the host runtime
   uint32_t window;          // 1: window rounds are exact (every token spans its string's length; a
                             // table that is not rank-monotone also has each eager candidate checked):
                             // the long-piece tiers also merge, in the same round, any pair ranked
-                            // below every other pair of its window (kernels.hip bpe_wave_seg)
+                            // below every other pair of its window (long.hip bpe_wave_seg)
   const uint32_t* wmeta;    // window: per id, the longest left side of a merge it is the right side of
                             // (bits 0-15) and the longest right side of one it is the left side of
   uint32_t compact;         // 1: entry values are new ids (strictly increasing in rank), else ranks
@@ -418,7 +419,7 @@ struct WinWork {
 hipError_t launch_win_len(const WinWork& w, hipStream_t s);
 hipError_t launch_win_rows(const WinWork& w, hipStream_t s);
 
-// ---- launchers (kernels.hip) -----------------------------------------------------------
+// ---- launchers (segment.hip, kernels.hip, long.hip, emit.hip, scan.hip, nfc.hip) ---------------
 void upload_done();
 // also zeroes the counters and nfc_bits; x: k_clear's launch options, x2: k_tilefirst's
 hipError_t launch_docstart(const Work& w, hipStream_t s, bool zero_counters, Lx x = {}, Lx x2 = {});
@@ -459,7 +460,7 @@ hipError_t scan_u64(uint64_t* inout, uint64_t n, uint64_t* tmp, uint64_t tmp_cap
 uint64_t scan_tmp_elems(uint64_t n_max);
 uint64_t tile_scan_tmp_elems(uint64_t n_tiles);  // scan_tmp (u64) that scan_tiles needs
 hipError_t shift_u64(uint64_t* p, uint64_t n, uint64_t delta, hipStream_t s);  // p[0, n) += delta
-// NFC splice (see kernels.hip): len[d] = flagged doc d's bytes (else 0); flagged docs' bytes
+// NFC splice (see nfc.hip): len[d] = flagged doc d's bytes (else 0); flagged docs' bytes
 // gathered to the sub-batch; the output's counts, offsets (out_off[0..n_docs]) and ids
 hipError_t launch_flag_docs(const uint64_t* off, uint64_t n_docs, const uint32_t* nfc_bits, uint32_t* flag, hipStream_t s);
 hipError_t launch_flag_len(const uint64_t* off, const uint32_t* flag, uint64_t n_docs, uint64_t* len, hipStream_t s);

@@ -899,7 +899,7 @@ void load_root(ctok* t, const ctj::Value& root) {
   }
 
 
-  // window rounds of the long-piece tiers (Tables::window, kernels.hip bpe_wave_seg): exact when
+  // window rounds of the long-piece tiers (Tables::window, long.hip bpe_wave_seg): exact when
   // every token instance spans exactly its string's length -- each byte's initial token is one
   // char, and every merge that can apply makes the token its two sides spell (no rank shift from
   // an invalid merge before it, src/bpe.rs:60-69); on a table that is not rank-monotone the

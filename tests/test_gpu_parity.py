@@ -143,9 +143,9 @@ def test_long_piece_tiers_and_order(request, fx):
     257..1024 and 1025..4096 B segmented tiers, > 4096 B global-memory tier) and random ones, as
     random letters, concatenated words and single-letter repeats.  Exercises k_long_len /
     k_long_order (length buckets, longest-first order) and the per-tier dynamic take
-    (kernels.hip), against the C oracle.  llama3_tt_path: the same vocab with the tiktoken-style
+    (long.hip), against the C oracle.  llama3_tt_path: the same vocab with the tiktoken-style
     merge list (several merges per token, not rank-monotone): the rounds of eager merges apply
-    their sites up to the first cascade (kernels.hip first_cascade)."""
+    their sites up to the first cascade (long.hip first_cascade)."""
     path = request.getfixturevalue(fx)
     with open(path) as f:
         obj = json.load(f)
@@ -198,7 +198,7 @@ def test_c3_tiktoken_layout_full_corpus(llama3_tt_path):
 
 @pytest.mark.parametrize("seed", range(6))
 def test_window_rounds_random_proper(seed):
-    """Window rounds of the segmented tiers (kernels.hip bpe_wave_seg, Tables::window) on random
+    """Window rounds of the segmented tiers (long.hip bpe_wave_seg, Tables::window) on random
     rank-monotone tables with tokens up to 8..23 letters (wide windows, model and CPU check in
     tests/test_window_rule.py): pieces of 2-3 letters at every tier's lengths, against the C
     oracle; the same table with an invalid merge in front (window rounds off) too."""
@@ -223,7 +223,7 @@ def test_window_rounds_random_proper(seed):
 @pytest.mark.parametrize("alpha", ["日本語", "かなカ", "한국어", "日a本", "\U0001F600\U0001F601", "éßø", "中文字符"])
 def test_window_rounds_random_proper_multibyte(alpha):
     """Window rounds on random rank-monotone tables over the UTF-8 bytes of multi-byte chars
-    (the C5 path of the dense tier's position windows, kernels.hip bpe_wave_dense): runs of 1..1500
+    (the C5 path of the dense tier's position windows, long.hip bpe_wave_dense): runs of 1..1500
     random chars of the alphabet (3- and 4-byte chars: pieces at every tier, most in the <= 256 B
     dense tier), against the C oracle; the same table with an invalid merge in front (rules off)."""
     seed = sum(map(ord, alpha)) % 1000
@@ -248,7 +248,7 @@ def test_window_rounds_random_proper_multibyte(alpha):
 @pytest.mark.parametrize("seed", range(8))
 def test_window_rounds_non_monotone(seed):
     """Window rounds on tables that are not rank-monotone (round 4: eager candidates checked
-    against their neighbours, kernels.hip bpe_wave_seg / bpe_wave_dense): a random proper table's
+    against their neighbours, long.hip bpe_wave_seg / bpe_wave_dense): a random proper table's
     merges shuffled, and re-laid out tiktoken-style (tests/test_window_rule.py _non_monotone), with
     runs at every long-piece tier's lengths, against the C oracle."""
     from tests.test_window_rule import _non_monotone
@@ -298,7 +298,7 @@ def test_c3_full_corpus(llama3_path):
 
 def test_eager_cascade_rounds():
     """toys.eager_cascade: after an "a b" merges, ("ab", "a") ranks below ("a", "b"), so a round
-    of that merge must stop at its first site whose new pairs rank lower (kernels.hip
+    of that merge must stop at its first site whose new pairs rank lower (long.hip
     first_cascade) -- in pieces of every long-piece tier (dense <= 256 B, segmented 257..4096 B,
     global-memory > 4096 B) and in the register passes, against the C oracle."""
     obj = toys.eager_cascade()

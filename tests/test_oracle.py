@@ -2,7 +2,7 @@
 own known-answer tests, the committed golden vectors, the `regex` module, and HF `tokenizers` on
 the input domain where the two provably agree.  Also pins, on the CPU, the
 piece-start rules the HIP pre-tokenizer kernel evaluates, per code point and in the
-bit-parallel form of kernels.hip k_segment."""
+bit-parallel form of segment.hip k_segment."""
 import hashlib
 import json
 import os
@@ -236,7 +236,7 @@ def test_gpu_segmentation_rules_equal_regex():
 
 
 def bitparallel_starts(text, docstart):
-    """Python transcription of kernels.hip k_segment: the piece-start predicate evaluated on
+    """Python transcription of segment.hip k_segment: the piece-start predicate evaluated on
     64-bit masks of 64-byte words (SegMasks / seg_derive), word neighbours carried across edges."""
     M = (1 << 64) - 1
     B = len(text)
@@ -457,7 +457,7 @@ def _eager_values(rt):
 
 
 def _rounds_bpe(rt, eager, text):
-    """The long-piece kernels' round structure in Python (kernels.hip first_cascade): per round
+    """The long-piece kernels' round structure in Python (long.hip first_cascade): per round
     the minimum rank r and its sites; a non-eager r merges every site at once ((x, x) runs: the
     1st, 3rd, ...); an eager r merges the sites left to right up to and including the first whose
     sequential new pairs -- (left neighbour, or nid after a merged site two tokens before; nid)

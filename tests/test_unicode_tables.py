@@ -58,7 +58,7 @@ def _two_level(s1, s2, per_byte):
     s2 = np.asarray(s2, dtype=np.int64)
     cp = np.arange(NCP, dtype=np.int64)
     blk = s1[cp >> 8]
-    if per_byte == 4:  # 2 bits per code point, 4 per byte (kernels.hip cls_of)
+    if per_byte == 4:  # 2 bits per code point, 4 per byte (dev_common.h cls_of)
         return (s2[blk * 64 + ((cp & 255) >> 2)] >> ((cp & 3) * 2)) & 3
     return s2[blk * 256 + (cp & 255)]
 

@@ -1,4 +1,4 @@
-"""The window rounds of the segmented long-piece tier (kernels.hip bpe_wave_seg) restated in
+"""The window rounds of the segmented long-piece tier (long.hip bpe_wave_seg) restated in
 Python (tests/window_model.py) against the reference's sequential merge loop (oracle/ref_py.py,
 src/bpe.rs:88-153): random rank-monotone tables with long tokens (wide windows), the Llama-3-shaped
 fixture on C3-like runs, and the round counts that make the rule worth it."""
@@ -73,7 +73,7 @@ def _non_monotone(seed):
 def test_window_rounds_non_monotone_tables(seed):
     """Window rounds on tables that are not rank-monotone (round 4): a candidate whose merge is
     eager also needs its new pairs with today's neighbours to rank above it and a window that covers
-    the neighbours' windows (kernels.hip bpe_wave_seg / bpe_wave_dense).  Against the reference loop."""
+    the neighbours' windows (long.hip bpe_wave_seg / bpe_wave_dense).  Against the reference loop."""
     alpha, rng, objs = _non_monotone(seed)
     for o in objs:
         tok = RefTokenizer(o)

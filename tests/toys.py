@@ -137,7 +137,7 @@ def random_proper(seed, alphabet="abc", n_merges=80, max_len=24):
     """A random rank-monotone table over the bytes of a few letters (multi-byte chars: their UTF-8
     bytes, merged in any grouping) (every merge's token exists before any merge
     consumes it is ranked, and no token is produced after one consuming it): the tables for which
-    the segmented tier's window rounds apply (kernels.hip bpe_wave_seg, Tables::window).  Long
+    the segmented tier's window rounds apply (long.hip bpe_wave_seg, Tables::window).  Long
     tokens make wide windows; the whole byte alphabet is in the vocab."""
     rng = random.Random(seed)
     chars = byte_chars()

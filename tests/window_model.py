@@ -1,4 +1,4 @@
-"""Python model of the segmented long-piece tier's window rounds (kernels.hip bpe_wave_seg,
+"""Python model of the segmented long-piece tier's window rounds (long.hip bpe_wave_seg,
 Tables::window) -- test infrastructure: tests/test_window_rule.py checks it against the
 sequential merge loop of the reference (oracle/ref_py.py RefTokenizer.bpe, src/bpe.rs:88-153).
 
@@ -38,7 +38,7 @@ def eager_set(tok):
 
 
 def _rank_sites(tok, t, rk, r, eager):
-    """The sites of rank r one round applies (kernels.hip): every one ((x, x) runs: 1st, 3rd, ...),
+    """The sites of rank r one round applies (long.hip): every one ((x, x) runs: 1st, 3rd, ...),
     or for an eager merge the sites up to the first whose sequential new pairs rank below r
     (first_cascade; (x, x): the leftmost alone)."""
     ranks, new_ids = tok.merge_ranks, tok.merge_new_ids
@@ -145,7 +145,7 @@ def window_bpe(tok, ids, k=64, max_groups=16, eager=None, eager_ext=True):
 
 def window_bpe_dense(tok, ids, eager=None):
     """The dense (<= 256 B) tier's window rounds: local minima only, the window scanned outward
-    from the pair over the tokens' first initial positions (kernels.hip bpe_wave_dense)."""
+    from the pair over the tokens' first initial positions (long.hip bpe_wave_dense)."""
     INF = 1 << 62
     left, right = window_meta(tok)
     eager = eager_set(tok) if eager is None else eager

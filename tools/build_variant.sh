@@ -3,7 +3,8 @@
 #   usage: bash tools/build_variant.sh REV OUT.so [-DNAME=VALUE ...]
 # REV "worktree" takes the working tree's sources.  The sources are copied to a scratch tree and
 # built there with the same Makefile (extra arguments are added to the compile flags, e.g. the
-# CTOK_* compile-time knobs of kernels.hip); the library is copied to OUT.so.
+# CTOK_* compile-time knobs: CTOK_CHECK in dev_common.h and emit.hip, CTOK_SEG_STAMPS in segment.hip,
+# CTOK_SHORT_NT in kernels.hip); the library is copied to OUT.so.
 set -e
 REV=$1; OUT=$2; shift 2
 DEFS="$*"
