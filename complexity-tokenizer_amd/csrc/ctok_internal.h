@@ -27,6 +27,14 @@ constexpr int kTile = kTileWords * 64;  // 3968 bytes per pre-tokenizer tile (pi
 constexpr int kTileSlots = 4096;        // per-tile stride of the piece-indexed arrays (pieces <= kTile)
 constexpr int kSegWaves = 4;            // tiles (wavefronts) per k_segment workgroup
 constexpr int kSegUnroll = 4;           // pieces per lane per routing round in k_segment
+// k_segment's per-wave buffer of a round's merged pieces, compacted in piece order: a whole
+// round's pieces, one byte each (the piece's index within the round).
+constexpr uint32_t kSegListBuf = 64 * kSegUnroll;
+// A merged piece's start within the tile (u16, < 4096) with its class marked on it: bits [12,15)
+// (0..2 class lists, 3 long, 6 class list 3).  Never 0xFFFF, which marks an unknown end.
+__host__ __device__ inline uint32_t seg_mark(uint32_t sl, uint32_t cls) { return sl | (cls << 12); }
+__host__ __device__ inline uint32_t seg_mark_start(uint32_t m) { return m & 0xFFFu; }
+__host__ __device__ inline uint32_t seg_mark_class(uint32_t m) { return m >> 12; }
 constexpr int kShortMax = 32;      // pieces up to this many bytes: classes 0..2 (and the generic pass)
 constexpr int kMedMax = 64;        // class 3: 33..64 B, still thread-per-piece (64 register slots)
 // Per-tile piece lists by length class: <= 8 B (whole-piece probe missed), 9..16 B, 17..32 B,

@@ -116,6 +116,14 @@ __device__ __forceinline__ uint32_t piece_probe(const Tables& t, uint4 e, uint32
   return kNone;
 }
 
+// The wave's LDS accesses before this point are ordered before those after it (its lanes hand
+// data to each other through LDS without a workgroup barrier).
+__device__ __forceinline__ void seg_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // position of the k-th (0-based) set bit of x (k < popcount(x))
 __device__ __forceinline__ uint32_t select_bit(uint64_t x, uint32_t k) {
   uint32_t pos = 0;
@@ -146,7 +154,8 @@ __device__ __forceinline__ uint32_t select_bit(uint64_t x, uint32_t k) {
 //     routing: a piece of <= 8 bytes that is one self-encoding vocab token is finished here with
 //     one whole-piece probe; every other piece is appended to its tile's class list (<= 8 B,
 //     9..16 B, 17..32 B) or to the long list, so that the merge passes run dense, length-uniform
-//     waves.
+//     waves.  A round is kSegUnroll slots of 64 pieces; the round's merged pieces are compacted
+//     in LDS and appended once per round (C4 k_segment 2.64 -> 2.52 ms, profiles/seg_routing/).
 // (amdgpu_waves_per_eu(7): at most 72 VGPRs, 7 waves per SIMD; without it the compiler takes 72-73
 // and this kernel runs at 6-7; C4 k_segment 2.78 -> 2.67 ms, 8 waves spill: 2.96 ms,
 // profiles/r03/v30_ab_seg_waves_per_eu.txt)
@@ -169,7 +178,8 @@ __device__ __forceinline__ uint32_t select_bit(uint64_t x, uint32_t k) {
 // paths in one kernel cost 18 more spilled SGPRs
 template <bool R16>
 __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(7))) void k_segment(Work w, Tables t) {
-  __shared__ uint16_t s_pos_all[kSegWaves][64 * kSegUnroll + 8];  // one round's piece starts
+  // one round's piece starts (later in the round a merged piece's class is marked on its start)
+  __shared__ uint16_t s_pos_all[kSegWaves][64 * kSegUnroll + 8];
   // per wave: 3 spare words, the 4 bytes before the context word, the context word, the tile, the
   // look-ahead word, the 4 bytes after it, 3 spare words (rows of 1032 words: every lane's 64-byte
   // word starts 16-byte aligned for its four 16-byte stores)
@@ -177,6 +187,7 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
   __shared__ uint64_t s_D_all[kSegWaves][64];
   constexpr uint32_t kSegLongCap = 32;  // long pieces staged per tile (the list entries)
   __shared__ uint64_t s_long_all[kSegWaves][kSegLongCap];
+  __shared__ uint8_t s_buf_all[kSegWaves][kSegListBuf];  // a round's merged pieces (phase C)
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wid = uni(threadIdx.x >> 6);
   const uint32_t tile = uni(blockIdx.x * kSegWaves + wid);
@@ -249,9 +260,7 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
         if (__ballot(mark(xs, ys)) != ~0ull) break;
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    seg_wave_sync();
     const int64_t x0 = g * 64;
     if (x0 < 0) D = 0;
     else if (x0 >= (int64_t)B) D = ~0ull;
@@ -280,9 +289,7 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
     }
     s_all[64 * 16] = v;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  seg_wave_sync();
   SEG_STAMP(1);
   if (m.NA) {  // non-ASCII code points: classes and NFC flags from the two-level tables
     constexpr int kSegCp = 4;
@@ -419,7 +426,7 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
     }
   }
   // documents starting in the tile: its words' doc-start bits within the text (summed at the end)
-  uint32_t nd = (!first && !last) ? (uint32_t)__popcll(D & valid) : 0u;
+  const uint32_t nd = uni(wave_sum_full_u32((!first && !last) ? (uint32_t)__popcll(D & valid) : 0u));
   const uint32_t c = (!first && !last) ? (uint32_t)__popcll(st) : 0u;
   const uint32_t inc = wave_incl_scan(c);
   if (!first && !last) w.wpref[(size_t)tile * 64 + lane - 1] = (uint16_t)(inc - c);
@@ -442,13 +449,80 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
   using RecT = typename std::conditional<R16, uint16_t, uint32_t>::type;
   RecT* prec = (RecT*)w.prec + (size_t)tile * kTileSlots;
   uint32_t* pdoc = w.pdoc + (size_t)tile * (kTileSlots / 32);
-  uint32_t hits = 0;
   uint32_t nm = 0;  // merged pieces so far (wave-uniform): the next ordinal
   uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;  // class-list lengths (wave-uniform)
   uint32_t nlong = 0;  // long pieces staged in s_long_all (wave-uniform)
-  uint32_t by0 = 0, by1 = 0, by2 = 0;        // this lane's bytes in class lists 0..2 (id regions)
+  // this lane's bytes in class lists 0..2 (the id regions) and its whole-piece hits, two 16-bit
+  // sums per register (a tile's are below 4096 each): by0 | by1 << 16, by2 | hits << 16
+  uint32_t by01 = 0, by2h = 0;
   constexpr int U = kSegUnroll;
   constexpr uint32_t W = 64 * U;  // pieces per round
+  static_assert(U == 4, "kSegUnroll: 4 (the probes of a round are unrolled by hand)");
+  // The round's merged pieces, compacted in piece order: s_buf[k] = the round's k-th merged
+  // piece (its index within the round), whose class is marked on its start in s_pos (seg_mark;
+  // every slot has read the raw starts and ends by then).  The list appends run once per 64
+  // compacted pieces (flush) instead of once per slot of 64 pieces of which ~9 are merged.
+  static_assert(kSegListBuf == W && W <= 256, "s_buf: a whole round's pieces, one byte each");
+  uint8_t* s_buf = s_buf_all[wid];
+  uint32_t cnt = 0;  // entries in s_buf (wave-uniform); the first one's ordinal is nm
+  // The walk over the compacted pieces, 64 per pass: class-0 spill, the four list appends, the
+  // id-region byte sums and the long-piece staging.  Entry i has ordinal nm + i.
+  auto flush = [&]() __attribute__((always_inline)) {
+    const uint64_t below = lanemask_lt();
+    for (uint32_t p0 = 0; p0 < cnt; p0 += 64) {
+      const uint32_t i = p0 + lane, ord = nm + i;
+      uint32_t bsl = 0, bn = 0;  // start; length (a long piece's: 0 when it ends past the look-ahead)
+      uint32_t cl = 4;  // 0..2 class lists, 3 long, 4 none, 6 class list 3
+      if (i < cnt) {
+        const uint32_t k = s_buf[i];
+        const uint32_t a = s_pos[k], el = s_pos[k + 1];  // (the next piece's start: marked or raw)
+        bsl = seg_mark_start(a);
+        cl = seg_mark_class(a);
+        bn = el == 0xFFFFu ? 0u : seg_mark_start(el) - bsl;
+      }
+      uint64_t m0 = __ballot(cl == 0);
+      // the tile's class-0 list is full: the rest of its class-0 pieces go to the long list (the
+      // first w.k0 of the tile, in piece order, stay)
+      if (n0 + (uint32_t)__popcll(m0) > w.k0) {
+        if (cl == 0 && n0 + (uint32_t)__popcll(m0 & below) >= w.k0) cl = 3;
+        m0 = __ballot(cl == 0);
+      }
+      const uint32_t e = list_entry(bsl, ord, bn);
+      {  // the wave owns its tile's lists: running counts in scalar registers, no atomics
+        const uint64_t m1 = __ballot(cl == 1), m2 = __ballot(cl == 2);
+        const uint64_t m3 = __ballot(cl == 6);
+        if (cl == 0) w.list0[(size_t)tile * w.k0 + n0 + __popcll(m0 & below)] = e;
+        if (cl == 1) w.list1[(size_t)tile * kCap1 + n1 + __popcll(m1 & below)] = e;
+        if (cl == 2) w.list2[(size_t)tile * kCap2 + n2 + __popcll(m2 & below)] = e;
+        if (cl == 6) w.list3[(size_t)tile * kCap3 + n3 + __popcll(m3 & below)] = e;
+        by01 += cl == 0 ? bn : cl == 1 ? bn << 16 : 0u;
+        by2h += cl == 2 ? bn : 0u;
+        n0 += __popcll(m0);
+        n1 += __popcll(m1);
+        n2 += __popcll(m2);
+        n3 += __popcll(m3);
+      }
+      const uint64_t lm = __ballot(cl == 3);
+      // long pieces staged in LDS; one global atomic for the tile's whole batch at the end (a
+      // returned atomic per round on the shared counter stalled the wave for its round trip).
+      // bn: the length when the piece ends within the look-ahead (0: k_long_len finds its end)
+      const uint64_t le = (uint64_t)(t0 + bsl) | ((uint64_t)ord << 32) | ((uint64_t)bn << 44);
+      if (lm && nlong + (uint32_t)__popcll(lm) <= kSegLongCap) {
+        if (cl == 3) s_long_all[wid][nlong + __popcll(lm & below)] = le;
+        nlong += (uint32_t)__popcll(lm);
+      } else if (lm) {  // (past kSegLongCap long pieces in the tile: one global atomic per pass)
+        const uint32_t leader = __ffsll((unsigned long long)lm) - 1;
+        uint32_t b = 0;
+        if (lane == leader) b = atomicAdd(&w.counters[kCtrLong], (uint32_t)__popcll(lm));
+        b = __builtin_amdgcn_readlane(b, leader);
+        const uint32_t li = b + __popcll(lm & below);
+        if (cl == 3 && li < w.long_cap) w.long_list[li] = le;
+        if (lane == leader && b + __popcll(lm) > w.long_cap) atomicOr(&w.counters[kCtrOverflow], 1u);
+      }
+    }
+    nm += cnt;
+    cnt = 0;
+  };
   for (uint32_t j0 = 0; j0 < np; j0 += W) {
     // expansion of this round's window [j0, j0 + W]: s_pos[j - j0] = start of piece j (the
     // entry past the window is the next round's first piece, peeked, not consumed).
@@ -481,9 +555,7 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
     }
 
     if (lane == 0 && np <= j0 + W) s_pos[np - j0] = (uint16_t)tile_end;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    seg_wave_sync();
     uint32_t sl[U], n[U], cls[U], plo[U], phi[U], h[U], doc[U];
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -503,7 +575,8 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
           cls[u] = generic ? 0 : n[u] > 32 ? 6 : n[u] > 16 ? 2 : n[u] > 8 ? 1 : 5;
         }
       }
-      // whole-piece probe key: the piece's raw bytes (from LDS), zero-padded to 8
+      // whole-piece probe key: the piece's raw bytes (from LDS), zero-padded to 8 (used by the
+      // probing lanes only, whose n is <= 8)
       const uint32_t a = sl[u] >> 2, sh = sl[u] & 3;
       const uint32_t d0 = s_text[a], d1 = s_text[a + 1], d2 = s_text[a + 2];
       const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, sh), w1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
@@ -518,12 +591,7 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
     uint32_t hitv[U];
 #define CTOK_PROBE_LOAD(u) const uint4 e##u = t.piece_tab[h[u]];
 #define CTOK_PROBE_USE(u) hitv[u] = piece_probe(t, e##u, h[u], plo[u], phi[u], n[u]);
-    static_assert(U == 4 || U == 8, "kSegUnroll: 4 or 8");
     CTOK_PROBE_LOAD(0) CTOK_PROBE_LOAD(1) CTOK_PROBE_LOAD(2) CTOK_PROBE_LOAD(3)
-    if constexpr (U == 8) {
-      CTOK_PROBE_LOAD(4) CTOK_PROBE_LOAD(5) CTOK_PROBE_LOAD(6) CTOK_PROBE_LOAD(7)
-      CTOK_PROBE_USE(4) CTOK_PROBE_USE(5) CTOK_PROBE_USE(6) CTOK_PROBE_USE(7)
-    }
     CTOK_PROBE_USE(0) CTOK_PROBE_USE(1) CTOK_PROBE_USE(2) CTOK_PROBE_USE(3)
 #undef CTOK_PROBE_LOAD
 #undef CTOK_PROBE_USE
@@ -536,104 +604,46 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
       if (cls[u] == 5) {
         const bool hit = hitv[u] != kNone;
         rec = hit ? hitv[u] : kRecMerged32;
-        hits += hit ? 1u : 0u;
+        by2h += hit ? 0x10000u : 0u;
         cls[u] = hit ? 4u : 0u;
       }
       // every piece's record: whole coalesced lines (u16 on narrow vocabularies)
       if (j < np) {
         prec[j] = (RecT)rec;
       }
-      const uint64_t dm = __ballot(j < np && doc[u]);  // doc-start bits of the 64 pieces
+      const uint64_t dm = __ballot(doc[u] != 0);  // doc-start bits of the 64 pieces
       if (lane == 0 && j0 + 64 * u < np)
         *reinterpret_cast<uint2*>(pdoc + ((j0 + 64 * u) >> 5)) = make_uint2((uint32_t)dm, (uint32_t)(dm >> 32));
     }
-    {  // the tile's class-0 list is full: the rest of its class-0 pieces go to the long list (one
-       // uniform test per round; the per-piece fix-up only in the rare round that crosses w.k0)
-      uint32_t tot0 = n0;
-#pragma unroll
-      for (int u = 0; u < U; u++) tot0 += (uint32_t)__popcll(__ballot(cls[u] == 0));
-      if (tot0 > w.k0) {
-        uint32_t c = n0;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-          const uint64_t m = __ballot(cls[u] == 0);
-          if (cls[u] == 0 && c + __popcll(m & lanemask_lt()) >= w.k0) cls[u] = 3;
-          c += (uint32_t)__popcll(m);
-        }
-      }
-    }
+    // per slot only the compaction: the piece's class marked on its start, its index within the
+    // round at its ordinal within the round
+    seg_wave_sync();  // every slot's s_pos reads before the first mark lands on them
 #pragma unroll
     for (int u = 0; u < U; u++) {
-      const uint64_t below = lanemask_lt();
-      // the piece's ordinal among the tile's merged pieces (inactive lanes have class 4)
       const uint64_t mm = __ballot(cls[u] != 4);
-      const uint32_t ord = nm + (uint32_t)__popcll(mm & below);
-      nm += (uint32_t)__popcll(mm);
-      const uint32_t e = list_entry(sl[u], ord, n[u]);
-      {  // the wave owns its tile's lists: running counts in scalar registers, no atomics
-        const uint64_t m0 = __ballot(cls[u] == 0);
-        const uint64_t m1 = __ballot(cls[u] == 1), m2 = __ballot(cls[u] == 2);
-        const uint64_t m3 = __ballot(cls[u] == 6);
-        if (cls[u] == 0) w.list0[(size_t)tile * w.k0 + n0 + __popcll(m0 & below)] = e;
-        if (cls[u] == 1) w.list1[(size_t)tile * kCap1 + n1 + __popcll(m1 & below)] = e;
-        if (cls[u] == 2) w.list2[(size_t)tile * kCap2 + n2 + __popcll(m2 & below)] = e;
-        if (cls[u] == 6) w.list3[(size_t)tile * kCap3 + n3 + __popcll(m3 & below)] = e;
-        by0 += cls[u] == 0 ? n[u] : 0u;
-        by1 += cls[u] == 1 ? n[u] : 0u;
-        by2 += cls[u] == 2 ? n[u] : 0u;
-        n0 += __popcll(m0);
-        n1 += __popcll(m1);
-        n2 += __popcll(m2);
-        n3 += __popcll(m3);
+      if (cls[u] != 4) {
+        s_pos[64 * u + lane] = (uint16_t)seg_mark(sl[u], cls[u]);
+        s_buf[cnt + (uint32_t)__popcll(mm & lanemask_lt())] = (uint8_t)(64 * u + lane);
       }
-      const uint64_t lm = __ballot(cls[u] == 3);
-      // long pieces staged in LDS; one global atomic for the tile's whole batch at the end (a
-      // returned atomic per round on the shared counter stalled the wave for its round trip)
-      if (lm && nlong + (uint32_t)__popcll(lm) <= kSegLongCap) {
-        if (cls[u] == 3) {
-          const uint32_t el = s_pos[64 * u + lane + 1];
-          const uint32_t ln = el == 0xFFFFu ? 0u : min(el - sl[u], 0x7FFFFu);
-          s_long_all[wid][nlong + __popcll(lm & lanemask_lt())] =
-              (uint64_t)(t0 + sl[u]) | ((uint64_t)ord << 32) | ((uint64_t)ln << 44);
-        }
-        nlong += (uint32_t)__popcll(lm);
-      } else if (lm) {  // (past kSegLongCap long pieces in the tile: one global atomic per wave)
-        const uint32_t leader = __ffsll((unsigned long long)lm) - 1;
-        uint32_t b = 0;
-        if (lane == leader) b = atomicAdd(&w.counters[kCtrLong], (uint32_t)__popcll(lm));
-        b = __builtin_amdgcn_readlane(b, leader);
-        const uint32_t li = b + __popcll(lm & lanemask_lt());
-        if (cls[u] == 3 && li < w.long_cap)
-        {
-          // the length when the piece ends within the look-ahead (0: k_long_len finds its end)
-          const uint32_t el = s_pos[64 * u + lane + 1];
-          const uint32_t ln = el == 0xFFFFu ? 0u : min(el - sl[u], 0x7FFFFu);
-          w.long_list[li] = (uint64_t)(t0 + sl[u]) | ((uint64_t)ord << 32) | ((uint64_t)ln << 44);
-        }
-        if (lane == leader && b + __popcll(lm) > w.long_cap) atomicOr(&w.counters[kCtrOverflow], 1u);
-      }
+      cnt += (uint32_t)__popcll(mm);
     }
+    seg_wave_sync();
+    flush();
     // every lane has read this round's s_pos before the next round's expansion overwrites it
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    seg_wave_sync();
   }
   if (nlong) {  // the tile's staged long pieces: one reservation, coalesced entry stores
     uint32_t b = 0;
     if (lane == 0) b = atomicAdd(&w.counters[kCtrLong], nlong);
     b = __builtin_amdgcn_readfirstlane(b);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    seg_wave_sync();
     if (lane < nlong && b + lane < w.long_cap) w.long_list[b + lane] = s_long_all[wid][lane];
     if (lane == 0 && b + nlong > w.long_cap) atomicOr(&w.counters[kCtrOverflow], 1u);
   }
   SEG_STAMP(4);
-  hits = wave_sum_full_u32(hits);
-  by0 = wave_sum_full_u32(by0);
-  by1 = wave_sum_full_u32(by1);
-  by2 = wave_sum_full_u32(by2);
-  nd = wave_sum_full_u32(nd);
+  by01 = wave_sum_full_u32(by01);
+  by2h = wave_sum_full_u32(by2h);
+  const uint32_t by0 = by01 & 0xFFFFu, by1 = by01 >> 16, by2 = by2h & 0xFFFFu, hits = by2h >> 16;
   if (lane == 0) {
     w.tile_tok[tile] = hits;  // initial token count (the merge passes add theirs atomically)
     w.tile_doc[tile] = nd;
