@@ -1,7 +1,7 @@
 // C++ host runtime behind the C ABI (include/ctok.h): the entry points on device and host
 // buffers -- decode, the host-buffer encode pipeline, padded encode, offsets -- and the GPU
-// pre-tokenizer for the trainer.  The loader is ctok_load.cpp, encode_device ctok_encode.cpp
-// (host_internal.h).
+// pre-tokenizer for the trainer.  The loader is ctok_load.cpp (with bpe_model.cpp and
+// table_compile.cpp), encode_device ctok_encode.cpp (host_internal.h).
 //
 // Reference counterparts (Complexity-ML/complexity-tokenizer v0.3.3):
 //   decode            src/huggingface/mod.rs:698-785, src/decoders.rs:74-119, parsing.rs:272-364

@@ -1,24 +1,20 @@
-// The tokenizer.json loader and table compiler of the host runtime, and the C ABI functions that
-// read only the loaded tokenizer (struct ctok).  Host-only: no HIP runtime call.
+// The tokenizer.json loader of the host runtime -- everything around the model: added tokens,
+// normalizer, pre-tokenizer, post-processor, decoder -- and the C ABI functions that read only the
+// loaded tokenizer (struct ctok).  The model itself is read by bpe_model.cpp and compiled into the
+// device tables by table_compile.cpp.  Host-only: no HIP runtime call.
 //
 // Reference counterparts (Complexity-ML/complexity-tokenizer v0.3.3):
 //   loader            src/huggingface/mod.rs:32-116 (schema), :159-166 (from_file), :247-334
-//   merge table       src/bpe.rs:52-79 (BpeTokenizer::new)
 //   normaliser choice src/huggingface/parsing.rs:10-90 (NFC default at :89)
 //   pre-tokenizer     src/huggingface/parsing.rs:92-190; src/pretokenizers.rs:71-126, :298-302
 //   vocab getters     src/vocab.rs:34-100, src/huggingface/mod.rs:856-866
 //   decode table      src/huggingface/mod.rs:698-785, src/decoders.rs:74-119, parsing.rs:272-364
-#include <sched.h>
-
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <sstream>
 #include <string_view>
-#include <thread>
 #include <unordered_set>
 
 #include "gen/regex_props.h"
@@ -27,69 +23,6 @@
 #include "knobs.h"
 
 namespace ctok_rt __attribute__((visibility("hidden"))) {
-
-// CPUs this process may run on: the affinity mask capped by the cgroup v2 quota (cpu.max), as
-// Rust's available_parallelism (rayon's default pool, reference src/huggingface/mod.rs:695)
-// counts them on Linux.  Cached: read once per process.
-unsigned usable_cpus_once() {
-  static const unsigned n = [] {
-    unsigned c = std::max(1u, std::thread::hardware_concurrency());
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof(set), &set) == 0) c = std::max(1, CPU_COUNT(&set));
-    if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-      char q[32] = {0};
-      unsigned long long period = 0;
-      if (fscanf(f, "%31s %llu", q, &period) == 2 && strcmp(q, "max") != 0 && period > 0) {
-        const unsigned long long quota = strtoull(q, nullptr, 10);
-        c = std::min<unsigned>(c, (unsigned)std::max<unsigned long long>(1, quota / period));
-      }
-      fclose(f);
-    }
-    return c;
-  }();
-  return n;
-}
-
-// ----------------------------------------------------------------------------- byte map
-// GPT-2 bytes_to_unicode (src/pretokenizers.rs:130-153): byte -> code point
-std::vector<uint32_t> byte_map() {
-  std::vector<int> bs;
-  for (int b = '!'; b <= '~'; b++) bs.push_back(b);
-  for (int b = 0xA1; b <= 0xAC; b++) bs.push_back(b);
-  for (int b = 0xAE; b <= 0xFF; b++) bs.push_back(b);
-  std::vector<uint32_t> cs(bs.begin(), bs.end());
-  uint32_t n = 0;
-  std::vector<bool> in(256, false);
-  for (int b : bs) in[b] = true;
-  for (int b = 0; b < 256; b++)
-    if (!in[b]) { bs.push_back(b); cs.push_back(256 + n++); }
-  std::vector<uint32_t> m(256);
-  for (size_t i = 0; i < 256; i++) m[bs[i]] = cs[i];
-  return m;
-}
-
-std::string utf8(uint32_t cp) {
-  std::string o;
-  if (cp < 0x80) o += (char)cp;
-  else if (cp < 0x800) { o += (char)(0xC0 | (cp >> 6)); o += (char)(0x80 | (cp & 0x3F)); }
-  else if (cp < 0x10000) { o += (char)(0xE0 | (cp >> 12)); o += (char)(0x80 | ((cp >> 6) & 0x3F)); o += (char)(0x80 | (cp & 0x3F)); }
-  else { o += (char)(0xF0 | (cp >> 18)); o += (char)(0x80 | ((cp >> 12) & 0x3F)); o += (char)(0x80 | ((cp >> 6) & 0x3F)); o += (char)(0x80 | (cp & 0x3F)); }
-  return o;
-}
-
-bool decode_utf8(const std::string& s, std::vector<uint32_t>& out) {
-  out.clear();
-  for (size_t i = 0; i < s.size();) {
-    uint8_t b = (uint8_t)s[i];
-    int len = b < 0x80 ? 1 : (b >> 5) == 6 ? 2 : (b >> 4) == 14 ? 3 : (b >> 3) == 30 ? 4 : 0;
-    if (!len || i + len > s.size()) return false;
-    uint32_t cp = len == 1 ? b : len == 2 ? (b & 0x1Fu) : len == 3 ? (b & 0x0Fu) : (b & 0x07u);
-    for (int k = 1; k < len; k++) cp = (cp << 6) | ((uint8_t)s[i + k] & 0x3Fu);
-    out.push_back(cp);
-    i += len;
-  }
-  return true;
-}
 
 int host_cls(uint32_t cp) {
   if (cp >= 0x110000) return 3;
@@ -172,24 +105,7 @@ bool is_white_space(uint32_t c) {  // Unicode White_Space (Rust char::is_whitesp
 
 std::string encode_utf8(const std::vector<uint32_t>& cps, size_t a, size_t b) {
   std::string s;
-  for (size_t i = a; i < b; i++) {
-    const uint32_t c = cps[i];
-    if (c < 0x80) {
-      s += (char)c;
-    } else if (c < 0x800) {
-      s += (char)(0xC0 | (c >> 6));
-      s += (char)(0x80 | (c & 63));
-    } else if (c < 0x10000) {
-      s += (char)(0xE0 | (c >> 12));
-      s += (char)(0x80 | ((c >> 6) & 63));
-      s += (char)(0x80 | (c & 63));
-    } else {
-      s += (char)(0xF0 | (c >> 18));
-      s += (char)(0x80 | ((c >> 12) & 63));
-      s += (char)(0x80 | ((c >> 6) & 63));
-      s += (char)(0x80 | (c & 63));
-    }
-  }
+  for (size_t i = a; i < b; i++) s += utf8(cps[i]);
   return s;
 }
 
@@ -594,11 +510,7 @@ void build_decode_table(ctok* t) {
   uint32_t n_ent = 0;
   for (const auto& kv : t->id_to_token) n_ent = std::max(n_ent, kv.first + 1);
   if (n_ent > (1u << 26)) throw_err(CTOK_E_UNSUPPORTED, "token ids above 2^26 are not supported by the decode table");
-  std::vector<int> inv(0x144, -1);  // GPT-2 char -> byte
-  {
-    std::vector<uint32_t> bm = byte_map();
-    for (int b = 0; b < 256; b++) inv[bm[b]] = b;
-  }
+  const std::vector<int> inv = byte_unmap();  // GPT-2 char -> byte
   std::unordered_set<std::string> special;
   for (const auto& sp : t->special) special.insert(sp.first);
   t->dec_ent.assign(2 * (size_t)n_ent, 0);
@@ -632,504 +544,105 @@ void build_decode_table(ctok* t) {
   for (int k = 0; k < 8; k++) t->dec_bytes.push_back(0);
 }
 
+// added tokens (mod.rs:103-116 schema, :274-305 maps): content -> (id, flags) in file order, a
+// later duplicate content replacing the earlier one; the special ones also into `special`
+using AddedTokens = std::vector<std::pair<std::string, std::pair<uint32_t, uint8_t>>>;
+
+AddedTokens parse_added_tokens(const ctj::Value* at, std::vector<std::pair<std::string, uint32_t>>& special_out) {
+  AddedTokens added;
+  if (!at) return added;
+  if (at->kind != ctj::Value::Array) throw_err(CTOK_E_PARSE, "invalid type for `added_tokens`, expected a sequence");
+  for (const auto& a : at->arr) {
+    if (a.kind != ctj::Value::Object) throw_err(CTOK_E_PARSE, "invalid type: expected struct AddedToken");
+    const ctj::Value* id = a.get("id");
+    const ctj::Value* content = a.get("content");
+    const ctj::Value* special = a.get("special");
+    if (!id) throw_err(CTOK_E_PARSE, "missing field `id`");
+    if (!content) throw_err(CTOK_E_PARSE, "missing field `content`");
+    if (!special) throw_err(CTOK_E_PARSE, "missing field `special`");
+    if (!id->is_u32()) throw_err(CTOK_E_PARSE, "invalid type for added token `id`, expected u32");
+    if (content->kind != ctj::Value::String) throw_err(CTOK_E_PARSE, "invalid type for added token `content`, expected a string");
+    if (special->kind != ctj::Value::Bool) throw_err(CTOK_E_PARSE, "invalid type for added token `special`, expected a boolean");
+    uint8_t flags = (get_bool_field(a, "single_word", false, "AddedToken") ? 1 : 0) |
+                    (get_bool_field(a, "lstrip", false, "AddedToken") ? 2 : 0) |
+                    (get_bool_field(a, "rstrip", false, "AddedToken") ? 4 : 0);
+    (void)get_bool_field(a, "normalized", false, "AddedToken");
+    bool replaced = false;
+    for (auto& e : added)
+      if (e.first == content->s) { e.second = {(uint32_t)id->u, flags}; replaced = true; }
+    if (!replaced) added.push_back({content->s, {(uint32_t)id->u, flags}});
+    if (special->b) {
+      bool rep = false;
+      for (auto& e : special_out)
+        if (e.first == content->s) { e.second = (uint32_t)id->u; rep = true; }
+      if (!rep) special_out.push_back({content->s, (uint32_t)id->u});
+    }
+  }
+  return added;
+}
+
+// The added tokens that can match inside a byte-mapped word, as raw-byte patterns (at_*), and
+// with them whether every id encode can emit fits 16 bits (ids16; after compile_tables: narrow)
+void compile_added_patterns(const AddedTokens& added, CompiledTables& t) {
+  const std::vector<int> inv = byte_unmap();
+  std::vector<uint32_t> cps;
+  std::string raw;
+  for (const auto& e : added) {
+    if (e.first.empty()) throw_err(CTOK_E_UNSUPPORTED, "added token with empty content: the reference's word loop never terminates (src/huggingface/mod.rs:569-610)");
+    if (!decode_utf8(e.first, cps) || !unmap_bytes(inv, cps, raw)) continue;
+    if (!can_occur_in_piece(raw)) continue;  // provably never matches inside a piece
+    t.at_bytes += raw;
+    t.at_off.push_back((uint32_t)t.at_bytes.size());
+    t.at_id.push_back(e.second.first);
+    t.at_flags.push_back(e.second.second);
+  }
+  t.ids16 = t.narrow;
+  for (uint32_t id : t.at_id) t.ids16 = t.ids16 && id < 0xFFFFu;
+}
+
+// add_prefix_space of the pre-tokenizer's one ByteLevel
+bool parse_byte_level(const ctj::Value* v) {
+  std::vector<std::pair<char, bool>> chain;
+  parse_pre_tokenizer(v, chain, 0);
+  int nbl = 0;
+  bool add_prefix_space = false;
+  for (auto& c : chain)
+    if (c.first == 'B') { nbl++; add_prefix_space = c.second; }
+  if (nbl != 1) throw_err(CTOK_E_UNSUPPORTED, "pre_tokenizer must contain exactly one ByteLevel");
+  return add_prefix_space;
+}
+
 void load(ctok* t, const char* buf, size_t len) {
-  // CTOK_LOAD_TIMING=1: per-phase load times on stderr
-  const bool lt = LoadKnobs().load_timing;
-  auto lt0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!lt) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[ctok load] %-12s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - lt0).count());
-    lt0 = now;
-  };
+  const LoadKnobs knobs;
+  LoadTimer timer{knobs.load_timing};
   ctj::Value root;
   try {
     root = ctj::parse(buf, len);
   } catch (const ctj::ParseError& e) {
     throw_err(CTOK_E_PARSE, e.what());
   }
-  lap("json");
-  load_root(t, root);
+  timer.lap("json");
+  load_root(t, root, knobs.tables, timer);
 }
 
 // The tokenizer from its parsed tokenizer.json value (from a file, a buffer, or built from tables
 // by ctok_create_from_tables).
-void load_root(ctok* t, const ctj::Value& root) {
-  const LoadKnobs knobs;
-  const bool lt = knobs.load_timing;
-  auto lt0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!lt) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[ctok load] %-12s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - lt0).count());
-    lt0 = now;
-  };
+void load_root(ctok* t, const ctj::Value& root, const TableOptions& opt, LoadTimer& timer) {
   if (root.kind != ctj::Value::Object) throw_err(CTOK_E_PARSE, "invalid type: expected struct TokenizerJson");
   const ctj::Value* model = root.get("model");
   if (!model) throw_err(CTOK_E_PARSE, "missing field `model`");
   if (model->kind != ctj::Value::Object) throw_err(CTOK_E_PARSE, "invalid type for `model`, expected struct ModelJson");
-  const ctj::Value* vocab = model->get("vocab");
-  if (!vocab) throw_err(CTOK_E_PARSE, "missing field `vocab`");
-  if (vocab->kind != ctj::Value::Object) throw_err(CTOK_E_PARSE, "invalid type for `vocab`, expected a map");
-  t->vocab.reserve(vocab->obj.size() * 2);
-  std::vector<const std::string*> first_keys;  // first occurrence of each key, in file order
-  first_keys.reserve(vocab->obj.size());
-  for (const auto& m : vocab->obj) {
-    if (!m.second.is_u32()) throw_err(CTOK_E_PARSE, "invalid value for vocab entry `" + m.first + "`, expected u32");
-    auto ins = t->vocab.try_emplace(m.first, (uint32_t)m.second.u);
-    if (ins.second) first_keys.push_back(&m.first);
-    else ins.first->second = (uint32_t)m.second.u;  // HashMap insert: a later duplicate key wins
-  }
-  // Vocab::id_to_token (src/vocab.rs:47-52).  Several tokens sharing one id make the reference's
-  // choice depend on HashMap order; here the later entry of the file wins (first occurrence of a
-  // key, final value) -- parity for such files is unpinned.
-  t->id_to_token.reserve(first_keys.size() * 2);
-  for (const std::string* k : first_keys) t->id_to_token[t->vocab.find(*k)->second] = *k;
-
-  lap("vocab");
-  // merges: deserialize_merges (mod.rs:56-101) then split(' ') == 2 parts (mod.rs:252-264)
-  std::vector<std::pair<std::string, std::string>> merges;
-  if (const ctj::Value* mv = model->get("merges")) {
-    if (mv->kind != ctj::Value::Array) throw_err(CTOK_E_PARSE, "invalid type for `merges`, expected a sequence of strings or arrays of two strings");
-    merges.reserve(mv->arr.size());
-    for (const auto& it : mv->arr) {
-      std::string s;
-      if (it.kind == ctj::Value::String) s = it.s;
-      else if (it.kind == ctj::Value::Array && it.arr.size() == 2 && it.arr[0].kind == ctj::Value::String &&
-               it.arr[1].kind == ctj::Value::String) s = it.arr[0].s + " " + it.arr[1].s;
-      else continue;
-      size_t sp = s.find(' ');
-      if (sp == std::string::npos || s.find(' ', sp + 1) != std::string::npos) continue;
-      merges.emplace_back(s.substr(0, sp), s.substr(sp + 1));
-    }
-  }
-  // BpeTokenizer::new (src/bpe.rs:52-79)
-  std::unordered_map<uint64_t, uint32_t> ranks;  // (a<<32|b) -> rank, last duplicate wins
-  ranks.reserve(merges.size() * 2);
-  std::vector<uint32_t> valid_new;
-  for (size_t r = 0; r < merges.size(); r++) {
-    auto ia = t->vocab.find(merges[r].first);
-    auto ib = t->vocab.find(merges[r].second);
-    if (ia == t->vocab.end() || ib == t->vocab.end()) continue;
-    auto in = t->vocab.find(merges[r].first + merges[r].second);
-    if (in == t->vocab.end()) continue;
-    ranks[((uint64_t)ia->second << 32) | ib->second] = (uint32_t)r;
-    valid_new.push_back(in->second);
-  }
-  lap("ranks");
-  if (merges.size() >= (size_t)kNoRank - 2) throw_err(CTOK_E_UNSUPPORTED, "more than 4M merges");
-  t->rank_newid = valid_new;
-  {
-    uint32_t max_id = 0;
-    for (const auto& kv : t->vocab) max_id = std::max(max_id, kv.second);
-    t->narrow = max_id < 0xFFFFu;
-  }
-  // compact table: values are the new ids themselves when new id is strictly increasing in rank
-  {
-    std::vector<std::pair<uint32_t, uint32_t>> rv;  // (rank, new id) of the entries that can merge
-    rv.reserve(ranks.size());
-    for (const auto& kv : ranks)
-      if (kv.second < valid_new.size()) rv.push_back({kv.second, valid_new[kv.second]});
-    std::sort(rv.begin(), rv.end());
-    t->compact = true;
-    for (size_t i = 1; i < rv.size(); i++)
-      if (rv[i].second <= rv[i - 1].second) { t->compact = false; break; }
-    if (knobs.force_wide) t->compact = false;
-  }
-  size_t cap = 1024;
-  // load factor <= 1/8: a lookup the Bloom filter lets through is often a pair with no merge,
-  // whose linear probe runs to an empty slot (C2 k_bpe_short 0.54 -> 0.48 ms against 1/2)
-  const size_t f42 = knobs.merge_slack;  // A/B knob
-  while (cap < ranks.size() * f42 + 16) cap <<= 1;
-  t->merge_tab.assign(cap, kEmpty);
-  t->merge_mask = (uint32_t)(cap - 1);
-  // inserted in rank order: the low-rank (frequent) pairs sit in their home slots, so their
-  // lookups end at the first probe (the same reason the whole-piece table is filled in id order)
-  std::vector<std::pair<uint32_t, uint64_t>> by_rank_key;
-  by_rank_key.reserve(ranks.size());
-  for (const auto& kv : ranks) by_rank_key.push_back({kv.second, kv.first});
-  std::sort(by_rank_key.begin(), by_rank_key.end());
-  for (const auto& rk : by_rank_key) {
-    const std::pair<uint64_t, uint32_t> kv{rk.second, rk.first};
-    uint32_t a = (uint32_t)(kv.first >> 32), b = (uint32_t)kv.first;
-    if (a > kMaxId || b > kMaxId) throw_err(CTOK_E_UNSUPPORTED, "token ids above 2^21-2 are not supported by the device merge table");
-    uint64_t val = kv.second;
-    if (t->compact) val = kv.second < valid_new.size() ? valid_new[kv.second] : kPanicVal;
-    uint64_t e = (val << 42) | ((uint64_t)a << kIdBits) | b;
-    uint32_t h = mhash(a, b) & t->merge_mask;
-    while (t->merge_tab[h] != kEmpty) h = (h + 1) & t->merge_mask;
-    t->merge_tab[h] = e;
-  }
-  for (uint32_t id : valid_new)
-    if (id > kMaxId) throw_err(CTOK_E_UNSUPPORTED, "token ids above 2^21-2 are not supported by the device merge table");
-  lap("merge_tab");
-  // byte-level initial ids: vocab[bytes_to_unicode[b]] (src/bpe.rs:94-97), -1 = dropped
-  std::vector<uint32_t> bm = byte_map();
-  for (int b = 0; b < 256; b++) {
-    auto it = t->vocab.find(utf8(bm[b]));
-    t->byte2id[b] = it == t->vocab.end() ? -1 : (int32_t)it->second;
-  }
-
-  // LDS image: hot table filled greedily in rank order (a pair whose two buckets are full stays
-  // global-only), Bloom filter over every entry (including the ones whose lookup panics).
-  // Byte-pair merges are left out of both: the merge passes look a pair up in LDS only after a
-  // merge, when one side is a merged (multi-byte) token; initial byte pairs use pair0.
-  {
-    std::vector<uint8_t> is_byte_tok(kMaxId + 2, 0);
-    for (int b = 0; b < 256; b++)
-      if (t->byte2id[b] >= 0 && (uint32_t)t->byte2id[b] <= kMaxId) is_byte_tok[t->byte2id[b]] = 1;
-    // image = hot table | Bloom filter of the pairs not in the hot table (the merge passes ask
-    // the filter only after a hot-table miss), then, outside the image, the Bloom filter of all
-    // pairs for the kernels that load the filter alone (k_bpe_wave without HOT)
-    t->lds_image.assign(kLdsImageBytes / 8 + kBloomWords / 2, 0);
-    uint64_t* hot = t->lds_image.data();
-    std::fill(hot, hot + kHotU64, kEmpty);
-    uint32_t* bloom = reinterpret_cast<uint32_t*>(hot + kHotU64);
-    uint32_t* bloom_all = reinterpret_cast<uint32_t*>(t->lds_image.data() + kLdsImageBytes / 8);
-    std::vector<std::pair<uint32_t, uint64_t>> by_rank;  // (rank, entry)
-    by_rank.reserve(ranks.size());
-    for (uint64_t e : t->merge_tab) {
-      if (e == kEmpty) continue;
-      const uint32_t a = (uint32_t)((e >> kIdBits) & ((1u << kIdBits) - 1)), b = (uint32_t)(e & ((1u << kIdBits) - 1));
-      if (is_byte_tok[a] && is_byte_tok[b]) continue;
-      by_rank.push_back({ranks.at(((uint64_t)a << 32) | b), e});
-    }
-    std::sort(by_rank.begin(), by_rank.end());
-    size_t placed = 0;
-    const bool use_hot = !knobs.no_hot_table;
-    for (const auto& re : by_rank) {
-      const uint64_t e = re.second;
-      const uint32_t a = (uint32_t)((e >> kIdBits) & ((1u << kIdBits) - 1)), b = (uint32_t)(e & ((1u << kIdBits) - 1));
-      const uint32_t h1 = mhash(a, b), h2 = mhash2(h1);
-      const uint32_t b1 = (h1 >> 12) & (kBloomBits - 1), b2 = (h2 >> 12) & (kBloomBits - 1);
-      bloom_all[b1 >> 5] |= 1u << (b1 & 31);
-      bloom_all[b2 >> 5] |= 1u << (b2 & 31);
-      uint64_t* slot = nullptr;
-      if (use_hot && re.first < valid_new.size()) {  // never cache an entry that panics
-        for (uint32_t c : {h1 & (kHotBuckets - 1), h2 & (kHotBuckets - 1)})
-          for (int k = 0; k < 2 && !slot; k++)
-            if (hot[2 * c + k] == kEmpty) slot = &hot[2 * c + k];
-      }
-      if (slot) {
-        *slot = e;
-        placed++;
-        continue;  // a hot pair is found in the hot table before the filter is asked
-      }
-      bloom[b1 >> 5] |= 1u << (b1 & 31);
-      bloom[b2 >> 5] |= 1u << (b2 & 31);
-    }
-    t->hot_entries = placed;
-    // narrow vocabularies: the same tables keyed by key16 (ctok_internal.h), for the register
-    // merge passes.  Global table: every entry, in rank order; hot table / Bloom filter: as above.
-    if (t->narrow) {
-      size_t cap16 = 1024;
-      // load <= 1/64: a lookup that reaches this table (a hot-table miss passing the Bloom filter)
-      // stops at its first slot almost always, and a wavefront waits for its slowest lane's
-      // probe chain -- C2 k_bpe_short 0.414 ms at 1/8, 0.391 at 1/32, 0.385 at 1/128 (A/B on one
-      // box, profiles/r02/v9_ab_merge16_load.txt); 32 MB for 50k merges
-      const size_t f16 = knobs.merge16_slack;
-      while (cap16 < ranks.size() * f16 + 16) cap16 <<= 1;
-      t->merge16.assign(cap16, kEmpty);
-      t->merge16_mask = (uint32_t)(cap16 - 1);
-      for (const auto& rk : by_rank_key) {
-        const uint32_t a = (uint32_t)(rk.second >> 32), b = (uint32_t)rk.second;
-        uint64_t val = rk.first;
-        if (t->compact) val = rk.first < valid_new.size() ? valid_new[rk.first] : kPanicVal;
-        uint32_t h = hash16_h(a, b) & t->merge16_mask;
-        while (t->merge16[h] != kEmpty) h = (h + 1) & t->merge16_mask;
-        t->merge16[h] = (val << 32) | key16(a, b);
-      }
-      t->lds16_image.assign(kLdsImageBytes / 8, 0);
-      uint64_t* hot16 = t->lds16_image.data();
-      std::fill(hot16, hot16 + kHotU64, kEmpty);
-      uint32_t* bloom16 = reinterpret_cast<uint32_t*>(hot16 + kHotU64);
-      for (const auto& re : by_rank) {
-        const uint64_t e = re.second;
-        const uint32_t a = (uint32_t)((e >> kIdBits) & ((1u << kIdBits) - 1)), b = (uint32_t)(e & ((1u << kIdBits) - 1));
-        const uint32_t h = hash16_h(a, b), g = hash16_g(a, b);
-        uint64_t* slot = nullptr;
-        if (use_hot && re.first < valid_new.size())
-          for (uint32_t c : {h >> 20, g >> 20})
-            for (int k = 0; k < 2 && !slot; k++)
-              if (hot16[2 * c + k] == kEmpty) slot = &hot16[2 * c + k];
-        if (slot) {
-          *slot = ((e >> 42) << 32) | key16(a, b);
-          continue;
-        }
-        const uint32_t b1 = h & (kBloomBits - 1), b2 = g >> 14;
-        bloom16[b1 >> 5] |= 1u << (b1 & 31);
-        bloom16[b2 >> 5] |= 1u << (b2 & 31);
-      }
-    }
-  }
-  lap("lds_image");
-  // rank monotonicity ("proper"): every merge consuming z ranks after every merge producing z
-  {
-    // per id (ids <= kMaxId, checked above): the latest rank producing it, the earliest consuming it
-    constexpr uint32_t kUnset = UINT32_MAX;
-    std::vector<uint32_t> maxprod(kMaxId + 2, kUnset), mincons(kMaxId + 2, kUnset);
-    for (const auto& kv : ranks) {
-      uint32_t r = kv.second;
-      if (r >= valid_new.size()) continue;  // panics on lookup anyway
-      uint32_t z = valid_new[r];
-      if (maxprod[z] == kUnset || maxprod[z] < r) maxprod[z] = r;
-      for (uint32_t c : {(uint32_t)(kv.first >> 32), (uint32_t)kv.first})
-        if (mincons[c] == kUnset || mincons[c] > r) mincons[c] = r;
-    }
-    t->proper = true;
-    for (size_t z = 0; z < maxprod.size(); z++)
-      if (maxprod[z] != kUnset && mincons[z] != kUnset && mincons[z] <= maxprod[z]) { t->proper = false; break; }
-    // per merge (bit at its table value: the rank, or the new id in a compact table): "eager"
-    // when a merge consuming its token ranks before it.  Only an eager merge can be followed at
-    // once by a merge of lower rank, so the long-piece rounds apply every occurrence of a
-    // non-eager merge together even when the table as a whole is not rank-monotone (tiktoken-
-    // style lists), and the leftmost one alone for an eager merge (ctok_internal.h Tables::eager).
-    t->eager_bits.assign(((t->compact ? kMaxId + 2 : valid_new.size()) + 31) / 32 + 1, 0u);
-    if (!t->proper) {
-      for (const auto& kv : ranks) {
-        const uint32_t r = kv.second;
-        if (r >= valid_new.size()) continue;
-        const uint32_t z = valid_new[r];
-        if (mincons[z] != kUnset && mincons[z] < r) {
-          const uint32_t v = t->compact ? z : r;
-          t->eager_bits[v >> 5] |= 1u << (v & 31);
-        }
-      }
-    }
-  }
-
-
-  // window rounds of the long-piece tiers (Tables::window, long.hip bpe_wave_seg): exact when
-  // every token instance spans exactly its string's length -- each byte's initial token is one
-  // char, and every merge that can apply makes the token its two sides spell (no rank shift from
-  // an invalid merge before it, src/bpe.rs:60-69); on a table that is not rank-monotone the
-  // kernels add a check for candidates whose merge is eager.
-  // Per id: the longest left side of a merge whose right side it is, and the longest right side
-  // of a merge whose left side it is (chars = bytes; 0xFFFF when longer).
-  {
-    auto nchars = [&](uint32_t id, bool& ok) -> uint32_t {
-      auto it = t->id_to_token.find(id);
-      if (it == t->id_to_token.end()) { ok = false; return 0; }
-      uint32_t c = 0;
-      for (unsigned char ch : it->second) c += (ch & 0xC0) != 0x80;
-      return c;
-    };
-    // (not rank-monotone: the kernels check each candidate whose merge is eager, bpe_wave_seg)
-    bool ok = !knobs.no_window;
-    for (int b = 0; b < 256 && ok; b++)
-      if (t->byte2id[b] >= 0 && nchars((uint32_t)t->byte2id[b], ok) != 1) ok = false;
-    uint32_t max_id = 0;
-    for (const auto& kv : t->vocab) max_id = std::max(max_id, kv.second);
-    std::vector<uint32_t> ml, mr;
-    if (ok) {
-      ml.assign((size_t)max_id + 1, 0);
-      mr.assign((size_t)max_id + 1, 0);
-    }
-    for (const auto& kv : ranks) {
-      if (!ok) break;
-      const uint32_t r = kv.second;
-      if (r >= valid_new.size()) continue;  // panics when looked up: never merges
-      const uint32_t a = (uint32_t)(kv.first >> 32), b = (uint32_t)kv.first;
-      const uint32_t la = nchars(a, ok), lb = nchars(b, ok), lz = nchars(valid_new[r], ok);
-      if (!ok || lz != la + lb || a > max_id || b > max_id) { ok = false; break; }
-      ml[b] = std::max(ml[b], la);
-      mr[a] = std::max(mr[a], lb);
-    }
-    t->window = ok;
-    if (ok) {
-      t->wmeta.resize((size_t)max_id + 1);
-      for (size_t i = 0; i <= max_id; i++) t->wmeta[i] = std::min(ml[i], 0xFFFFu) | std::min(mr[i], 0xFFFFu) << 16;
-    }
-  }
-  lap("window");
-
-  // byte-pair table: the merge-table value of (byte2id[a], byte2id[b]) for every byte pair a, b
-  // (the initial pairs of every piece are byte pairs), kNoRank where the pair has no merge
-  t->pair0.assign(65536, kNoRank);
-  for (uint32_t a = 0; a < 256; a++)
-    for (uint32_t b = 0; b < 256; b++) {
-      if (t->byte2id[a] < 0 || t->byte2id[b] < 0) continue;
-      auto it = ranks.find(((uint64_t)(uint32_t)t->byte2id[a] << 32) | (uint32_t)t->byte2id[b]);
-      if (it == ranks.end()) continue;
-      const uint32_t r = it->second;
-      t->pair0[a * 256 + b] = t->compact ? (r < valid_new.size() ? valid_new[r] : kPanicVal) : r;
-    }
-  // The packed 16-slot tier of k_bpe_short (merge_packed_hd.h) keeps table values as u16 with 0xFFFF
-  // for "none": every value it can see -- the byte-pair table, the narrow global table, the narrow
-  // hot table -- must be below 0xFFFF, and none may be one whose lookup panics (the tier does not
-  // check for those).  Compact tables (value = new id) of a narrow vocabulary without panicking
-  // entries qualify; the tier is built for compact tables only.
-  if (t->narrow && t->compact) {
-    auto fits = [&](uint32_t v) { return v < 0xFFFFu; };  // (kPanicVal is above it)
-    bool ok = true;
-    for (uint32_t v : t->pair0) ok = ok && (v == kNoRank || fits(v));
-    for (uint64_t e : t->merge16) ok = ok && (e == kEmpty || fits((uint32_t)(e >> 32)));
-    for (uint32_t i = 0; i < kHotU64; i++) {
-      const uint64_t e = t->lds16_image[i];
-      ok = ok && (e == kEmpty || fits((uint32_t)(e >> 32)));
-    }
-    t->short_packed = ok;
-  }
-  if (lt) fprintf(stderr, "[ctok load] narrow %d compact %d short_packed %d\n", (int)t->narrow, (int)t->compact, (int)t->short_packed);
-
-  lap("proper+pair0");
-  // whole-piece table: every vocab entry of <= 8 raw bytes whose own BPE is that single token
-  {
-    std::vector<int> inv0(0x144, -1);  // mapped code point (< U+0144) -> byte
-    for (int b = 0; b < 256; b++) inv0[bm[b]] = b;
-    // the merge table probed as the kernels probe it: value = rank, or (compact) the new id,
-    // both increasing in rank; kPanicVal / a rank past the valid merges would panic
-    auto tab_value = [&](uint32_t a, uint32_t b) -> uint64_t {
-      const uint64_t key = ((uint64_t)a << kIdBits) | b;
-      for (uint32_t h = mhash(a, b) & t->merge_mask;; h = (h + 1) & t->merge_mask) {
-        const uint64_t e = t->merge_tab[h];
-        if (e == kEmpty) return UINT64_MAX;
-        if ((e & ((1ull << 42) - 1)) == key) return e >> 42;
-      }
-    };
-    const uint64_t n_valid = valid_new.size();
-    auto panics = [&](uint64_t v) { return t->compact ? v == kPanicVal : v >= n_valid; };
-    std::vector<std::pair<const std::string*, uint32_t>> items;
-    items.reserve(t->vocab.size());
-    for (const auto& kv : t->vocab) items.push_back({&kv.first, kv.second});
-    // the reference merge loop (src/bpe.rs:88-153) on each entry's bytes, vocab split over threads
-    const unsigned nth = std::min(16u, usable_cpus_once());
-    std::vector<std::vector<std::pair<std::string, uint32_t>>> part(nth);
-    auto work = [&](unsigned w) {
-      std::vector<uint32_t> cps, tk;
-      for (size_t i = w; i < items.size(); i += nth) {
-        const std::string& key = *items[i].first;
-        if (!decode_utf8(key, cps) || cps.empty() || cps.size() > 8) continue;
-        std::string raw;
-        bool ok = true;
-        for (uint32_t c : cps) {
-          if (c >= inv0.size() || inv0[c] < 0) { ok = false; break; }
-          raw += (char)inv0[c];
-        }
-        if (!ok) continue;
-        tk.clear();
-        for (unsigned char c : raw) {
-          if (t->byte2id[c] < 0) { ok = false; break; }
-          tk.push_back((uint32_t)t->byte2id[c]);
-        }
-        if (!ok) continue;
-        for (;;) {
-          size_t bi = 0;
-          uint64_t best = UINT64_MAX;
-          for (size_t j = 0; j + 1 < tk.size(); j++) {
-            const uint64_t v = tab_value(tk[j], tk[j + 1]);
-            if (v == UINT64_MAX) continue;
-            if (panics(v)) { ok = false; break; }  // would panic: leave to the kernels
-            if (v < best) { best = v; bi = j; }
-          }
-          if (!ok || best == UINT64_MAX) break;
-          tk[bi] = t->compact ? (uint32_t)best : valid_new[best];
-          tk.erase(tk.begin() + bi + 1);
-        }
-        if (ok && tk.size() == 1 && tk[0] == items[i].second) part[w].push_back({raw, items[i].second});
-      }
-    };
-    {
-      std::vector<std::thread> th;
-      for (unsigned w = 1; w < nth; w++) th.emplace_back(work, w);
-      work(0);
-      for (auto& x : th) x.join();
-    }
-    std::vector<std::pair<std::string, uint32_t>> ents;
-    for (auto& p : part)
-      for (auto& e : p) ents.push_back(std::move(e));
-    // id order (BPE ids grow with merge order, roughly inverse frequency): frequent pieces are
-    // inserted first and sit in their home slots -- k_segment's probes mostly end at the first
-    // slot (C2 k_segment 0.42 -> 0.32 ms against the hash-map order used before)
-    std::sort(ents.begin(), ents.end(), [](const auto& x, const auto& y) { return x.second < y.second; });
-    size_t pcap = 1024;
-    const size_t fp = knobs.piece_slack;  // A/B knob
-    while (pcap < ents.size() * fp + 16) pcap <<= 1;  // load <= 1/8: misses end early (C2 k_segment -10%)
-    t->piece_tab.assign((pcap + 1) * 4, 0);  // + one slot that stays empty (k_segment's no-probe lanes)
-    t->piece_mask = (uint32_t)(pcap - 1);
-    for (const auto& e : ents) {
-      uint64_t v = 0;
-      for (size_t i = 0; i < e.first.size(); i++) v |= (uint64_t)(uint8_t)e.first[i] << (8 * i);
-      const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32), len = (uint32_t)e.first.size();
-      uint32_t h = piece_hash(lo, hi, len) & t->piece_mask;
-      while (t->piece_tab[4 * h + 2] != 0) h = (h + 1) & t->piece_mask;
-      t->piece_tab[4 * h] = lo;
-      t->piece_tab[4 * h + 1] = hi;
-      t->piece_tab[4 * h + 2] = len;
-      t->piece_tab[4 * h + 3] = e.second;
-    }
-    if (knobs.no_piece_table) std::fill(t->piece_tab.begin(), t->piece_tab.end(), 0u);
-  }
-
-  lap("piece_tab");
-  // added tokens (mod.rs:103-116 schema, :274-305 maps)
-  std::vector<std::pair<std::string, std::pair<uint32_t, uint8_t>>> added;  // content -> (id, flags)
-  if (const ctj::Value* at = root.get("added_tokens")) {
-    if (at->kind != ctj::Value::Array) throw_err(CTOK_E_PARSE, "invalid type for `added_tokens`, expected a sequence");
-    for (const auto& a : at->arr) {
-      if (a.kind != ctj::Value::Object) throw_err(CTOK_E_PARSE, "invalid type: expected struct AddedToken");
-      const ctj::Value* id = a.get("id");
-      const ctj::Value* content = a.get("content");
-      const ctj::Value* special = a.get("special");
-      if (!id) throw_err(CTOK_E_PARSE, "missing field `id`");
-      if (!content) throw_err(CTOK_E_PARSE, "missing field `content`");
-      if (!special) throw_err(CTOK_E_PARSE, "missing field `special`");
-      if (!id->is_u32()) throw_err(CTOK_E_PARSE, "invalid type for added token `id`, expected u32");
-      if (content->kind != ctj::Value::String) throw_err(CTOK_E_PARSE, "invalid type for added token `content`, expected a string");
-      if (special->kind != ctj::Value::Bool) throw_err(CTOK_E_PARSE, "invalid type for added token `special`, expected a boolean");
-      uint8_t flags = (get_bool_field(a, "single_word", false, "AddedToken") ? 1 : 0) |
-                      (get_bool_field(a, "lstrip", false, "AddedToken") ? 2 : 0) |
-                      (get_bool_field(a, "rstrip", false, "AddedToken") ? 4 : 0);
-      (void)get_bool_field(a, "normalized", false, "AddedToken");
-      bool replaced = false;
-      for (auto& e : added)
-        if (e.first == content->s) { e.second = {(uint32_t)id->u, flags}; replaced = true; }
-      if (!replaced) added.push_back({content->s, {(uint32_t)id->u, flags}});
-      if (special->b) {
-        bool rep = false;
-        for (auto& e : t->special)
-          if (e.first == content->s) { e.second = (uint32_t)id->u; rep = true; }
-        if (!rep) t->special.push_back({content->s, (uint32_t)id->u});
-      }
-    }
-  }
-  // added tokens that can match inside a byte-mapped word, as raw-byte patterns
-  std::unordered_map<uint32_t, int> inv;  // mapped code point -> byte
-  for (int b = 0; b < 256; b++) inv[bm[b]] = b;
-  for (const auto& e : added) {
-    if (e.first.empty()) throw_err(CTOK_E_UNSUPPORTED, "added token with empty content: the reference's word loop never terminates (src/huggingface/mod.rs:569-610)");
-    std::vector<uint32_t> cps;
-    if (!decode_utf8(e.first, cps)) continue;
-    std::string raw;
-    bool ok = true;
-    for (uint32_t c : cps) {
-      auto it = inv.find(c);
-      if (it == inv.end()) { ok = false; break; }
-      raw += (char)it->second;
-    }
-    if (!ok || !can_occur_in_piece(raw)) continue;  // provably never matches inside a piece
-    t->at_bytes += raw;
-    t->at_off.push_back((uint32_t)t->at_bytes.size());
-    t->at_id.push_back(e.second.first);
-    t->at_flags.push_back(e.second.second);
-  }
-
-  t->ids16 = t->narrow;
-  for (uint32_t id : t->at_id) t->ids16 = t->ids16 && id < 0xFFFFu;
+  const BpeModel m = parse_model(*model, t->vocab, t->id_to_token, timer);
+  compile_tables(m, opt, *t, timer);
+  compile_added_patterns(parse_added_tokens(root.get("added_tokens"), t->special), *t);
   t->nfc = parse_normalizer(root.get("normalizer")) != 0;
-  std::vector<std::pair<char, bool>> chain;
-  parse_pre_tokenizer(root.get("pre_tokenizer"), chain, 0);
-  int nbl = 0;
-  for (auto& c : chain)
-    if (c.first == 'B') { nbl++; t->add_prefix_space = c.second; }
-  if (nbl != 1) throw_err(CTOK_E_UNSUPPORTED, "pre_tokenizer must contain exactly one ByteLevel");
-
-  // decoder (parsing.rs:272-364) and the per-id decode table
+  t->add_prefix_space = parse_byte_level(root.get("pre_tokenizer"));
   parse_post_processor(t, root.get("post_processor"));
   t->decoder = parse_decoder(root.get("decoder"), t->decoder_name);
   build_decode_table(t);
-  lap("rest");
+  timer.lap("rest");
 }
+
 
 }  // namespace ctok_rt
 
@@ -1216,7 +729,9 @@ int ctok_create_from_tables(const ctok_tables* tb, ctok** out) {
     root.obj.emplace_back("pre_tokenizer", std::move(pre));
     root.obj.emplace_back("decoder", std::move(dec));
     auto t = std::make_unique<ctok>();
-    load_root(t.get(), root);
+    const LoadKnobs knobs;
+    LoadTimer timer{knobs.load_timing};
+    load_root(t.get(), root, knobs.tables, timer);
     *out = t.release();
   });
 }

@@ -1,7 +1,9 @@
 // Internals of the host runtime shared by its translation units: error plumbing, the tokenizer
 // object, the per-device state and the few functions that cross files.  Not part of the C ABI
 // (hidden visibility: libctok.so exports the C functions of include/ctok.h only).
-//   ctok_load.cpp    tokenizer.json loader, table compiler, the getters that read only struct ctok
+//   bpe_model.cpp    tokenizer.json's model as a BpeModel (HIP-free, table_compile.h)
+//   table_compile.cpp  the BpeModel into the device tables, CompiledTables (HIP-free, table_compile.h)
+//   ctok_load.cpp    the rest of the tokenizer.json loader, the getters that read only struct ctok
 //   ctok_encode.cpp  device state (table upload), encode_device and the NFC splice
 //   ctok_host.cpp    decode, host-buffer pipeline, padded encode, offsets, pretokenize, C ABI
 #pragma once
@@ -24,6 +26,7 @@
 #include "ctok_internal.h"
 #include "host_common.h"
 #include "json.hpp"
+#include "table_compile.h"
 
 namespace ctok_rt __attribute__((visibility("hidden"))) {
 using namespace ctok_dev;
@@ -36,13 +39,7 @@ inline int fail(int code, const std::string& msg) {
   return code;
 }
 
-struct CtokError {
-  int code;
-  std::string msg;
-};
-
-[[noreturn]] inline void throw_err(int code, const std::string& msg) { throw CtokError{code, msg}; }
-
+// (CtokError and throw_err: table_compile.h)
 #define HIPTRY(x)                                                                                   \
   do {                                                                                              \
     hipError_t e_ = (x);                                                                            \
@@ -269,36 +266,14 @@ struct DeviceState {
 
 // ----------------------------------------------------------------------------- tokenizer
 
-struct ctok {
+// (the compiled tables: its CompiledTables base, table_compile.h)
+struct ctok : ctok_rt::CompiledTables {
   // host-side model (immutable after load)
   std::unordered_map<std::string, uint32_t> vocab;          // model.vocab
   std::unordered_map<uint32_t, std::string> id_to_token;    // Vocab::id_to_token
   std::vector<std::pair<std::string, uint32_t>> special;    // special added tokens
   bool nfc = true;
   bool add_prefix_space = false;
-  // compiled tables
-  std::vector<uint64_t> merge_tab;
-  uint32_t merge_mask = 0;
-  std::vector<uint64_t> lds_image;  // kLdsImageBytes: hot table + Bloom filter
-  std::vector<uint64_t> lds16_image, merge16;  // narrow vocabularies: the 32-bit-key tables (key16)
-  uint32_t merge16_mask = 0;
-  std::vector<uint32_t> pair0;      // 256 x 256 byte-pair merge values
-  size_t hot_entries = 0;
-  std::vector<uint32_t> piece_tab;  // 4 u32 per slot (see ctok_internal.h piece_hash)
-  uint32_t piece_mask = 0;
-  std::vector<uint32_t> rank_newid;
-  std::vector<uint32_t> eager_bits;  // bit v: the merge of table value v is eager (see Tables::eager)
-  std::vector<uint32_t> wmeta;       // window rounds (Tables::wmeta): per id, max left | max right << 16
-  bool window = false;               // window rounds exact for this table (see Tables::window)
-  int32_t byte2id[256];
-  std::string at_bytes;
-  std::vector<uint32_t> at_off{0}, at_id;
-  std::vector<uint8_t> at_flags;
-  bool proper = true;
-  bool compact = false;
-  bool narrow = false;  // every vocab id < 2^16
-  bool short_packed = false;  // narrow, and every narrow-table value fits the packed 16-slot tier (Tables::short_packed)
-  bool ids16 = false;   // every id encode can emit (vocab and added tokens) < 2^16: 16-bit ids on PCIe
   // decode (src/huggingface/mod.rs:710-747): decoder kind, per-id decoded bytes
   int decoder = 1;                  // 1 ByteLevel, 0 raw concatenation (unknown decoder type), -1 unsupported
   std::string decoder_name;         // for the unsupported message
@@ -323,12 +298,10 @@ struct ctok {
 namespace ctok_rt __attribute__((visibility("hidden"))) {
 
 // ---- ctok_load.cpp
-unsigned usable_cpus_once();
-bool decode_utf8(const std::string& s, std::vector<uint32_t>& out);
 std::string encode_utf8(const std::vector<uint32_t>& cps, size_t a, size_t b);
 bool is_white_space(uint32_t c);
 void load(ctok* t, const char* buf, size_t len);
-void load_root(ctok* t, const ctj::Value& root);
+void load_root(ctok* t, const ctj::Value& root, const TableOptions& opt, LoadTimer& timer);
 
 // ---- ctok_encode.cpp
 double now_ms();

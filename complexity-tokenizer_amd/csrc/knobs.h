@@ -5,8 +5,9 @@
 #include <cstdlib>
 #include <optional>
 
-#include "ctok_internal.h"
 #include "chunk_sort_hd.h"
+#include "ctok_internal.h"
+#include "table_compile.h"
 
 namespace ctok_rt __attribute__((visibility("hidden"))) {
 
@@ -20,16 +21,21 @@ inline std::optional<uint64_t> env_u64(const char* name) {
   return v ? std::optional<uint64_t>(strtoull(v, nullptr, 10)) : std::nullopt;
 }
 
-// Read when a tokenizer's tables are compiled (load / load_root): A/B arms of the table compiler
+// Read once per load (load, ctok_create_from_tables): the timing switch and the A/B arms of the
+// table compiler (TableOptions, table_compile.h, which holds their defaults)
 struct LoadKnobs {
   bool load_timing = env_set("CTOK_LOAD_TIMING");
-  bool force_wide = env_set("CTOK_FORCE_WIDE");
-  bool no_hot_table = env_set("CTOK_NO_HOT_TABLE");
-  bool no_window = env_set("CTOK_NO_WINDOW");
-  bool no_piece_table = env_set("CTOK_NO_PIECE_TABLE");
-  size_t merge_slack = (size_t)env_int("CTOK_MERGE_SLACK", 8);
-  size_t merge16_slack = (size_t)env_int("CTOK_MERGE16_SLACK", 64);
-  size_t piece_slack = (size_t)env_int("CTOK_PIECE_SLACK", 8);
+  TableOptions tables = [] {
+    TableOptions o;
+    o.force_wide = env_set("CTOK_FORCE_WIDE");
+    o.no_hot_table = env_set("CTOK_NO_HOT_TABLE");
+    o.no_window = env_set("CTOK_NO_WINDOW");
+    o.no_piece_table = env_set("CTOK_NO_PIECE_TABLE");
+    o.merge_slack = (size_t)env_int("CTOK_MERGE_SLACK", (int)o.merge_slack);
+    o.merge16_slack = (size_t)env_int("CTOK_MERGE16_SLACK", (int)o.merge16_slack);
+    o.piece_slack = (size_t)env_int("CTOK_PIECE_SLACK", (int)o.piece_slack);
+    return o;
+  }();
 };
 
 // Read when the tables are uploaded to a device (device_state): what Tables says of them

@@ -88,7 +88,7 @@ __device__ __forceinline__ uint32_t resolve_rank(const Tables& t, uint64_t key, 
 
 __device__ __forceinline__ uint64_t pair_key(uint32_t a, uint32_t b) { return ((uint64_t)a << kIdBits) | b; }
 
-// The LDS image of the merge passes: hot table + Bloom filter (ctok_internal.h).
+// The LDS image of the merge passes: hot table + Bloom filter (pair_tables_hd.h).
 struct PairLds {
   const lds_u64* hot;  // bucket c = hot[2c], hot[2c + 1]
   const lds_u32* bloom;
@@ -129,7 +129,7 @@ __device__ __forceinline__ uint32_t rank_lds(const PairLds& P, uint32_t a, uint3
 // One pair lookup of a merge pass, split in two so that the global-table load (issued by
 // start, only when the LDS stage cannot decide) overlaps the caller's other work before finish.
 // NARROW = false: the 42-bit-key tables (mhash / mhash2); true: the 32-bit-key tables (key16,
-// ctok_internal.h), whose hashes and bucket compares take about half the VALU.
+// pair_tables_hd.h), whose hashes and bucket compares take about half the VALU.
 template <bool NARROW, bool HOT> struct Probe;
 
 template <bool HOT>
