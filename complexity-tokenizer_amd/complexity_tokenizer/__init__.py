@@ -24,7 +24,7 @@ from . import _native as _n
 from . import _fast  # the Python-object edges of encode_batch (csrc/pyfast.c); built with libctok.so
 
 __version__ = "0.3.3"
-__all__ = ["Tokenizer", "Trainer", "Encoding", "BatchEncoding", "PanicException", "UnsupportedConfigError",
+__all__ = ["Tokenizer", "Trainer", "BpeTrainer", "Encoding", "BatchEncoding", "PanicException", "UnsupportedConfigError",
            "DeviceError", "__version__"]
 
 
@@ -154,6 +154,7 @@ def _split_lists(flat: np.ndarray, off: np.ndarray) -> list:
 
 from .encoding import BatchEncoding, Encoding  # noqa: E402
 from .trainer import Trainer  # noqa: E402
+from .bpe_trainer import BpeTrainer  # noqa: E402
 
 
 class Tokenizer:

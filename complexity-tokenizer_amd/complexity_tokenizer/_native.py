@@ -135,6 +135,24 @@ class TrainerCountStats(ctypes.Structure):  # include/ctok_trainer.h ctok_traine
                 ("bytes_d2h", ctypes.c_uint64), ("ms_device", ctypes.c_double), ("ms_host", ctypes.c_double)]
 
 
+class BpeTrainerConfig(ctypes.Structure):  # include/ctok_bpe_trainer.h
+    _fields_ = [("vocab_size", ctypes.c_uint64), ("min_frequency", ctypes.c_uint32),
+                ("special", ctypes.c_char_p), ("special_off", ctypes.POINTER(ctypes.c_uint64)),
+                ("n_special", ctypes.c_uint64), ("end_of_word_suffix", ctypes.c_char_p),
+                ("continuing_subword_prefix", ctypes.c_char_p), ("show_progress", ctypes.c_int),
+                ("device", ctypes.c_int)]
+
+
+class BpeStrings(ctypes.Structure):  # include/ctok_bpe_trainer.h ctok_bpe_strings
+    _fields_ = [("bytes", ctypes.c_void_p), ("off", ctypes.POINTER(ctypes.c_uint64)), ("n", ctypes.c_uint64)]
+
+
+class BpeTrainerStats(ctypes.Structure):  # include/ctok_bpe_trainer.h ctok_bpe_trainer_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("words", "unique_words", "initial_symbols", "merges", "table_capacity",
+                                               "rebuilds", "chunks", "host_chunks", "rerun_chunks")] + \
+               [(k, ctypes.c_double) for k in ("ms_count", "ms_pairs", "ms_best", "ms_merges", "ms_host")]
+
+
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -195,6 +213,21 @@ SIGS = {
                                            ctypes.POINTER(ctypes.c_double)]),
     "ctok_trainer_word_counts": (ctypes.c_int, [_p, ctypes.c_int, _p, _u64, _p, _p, _u64, _u64p, _u64p]),
     "ctok_trainer_count_stats": (ctypes.c_int, [_p, ctypes.POINTER(TrainerCountStats)]),
+    # include/ctok_bpe_trainer.h
+    "ctok_bpe_trainer_create": (ctypes.c_int, [ctypes.POINTER(BpeTrainerConfig), ctypes.POINTER(_p)]),
+    "ctok_bpe_trainer_destroy": (None, [_p]),
+    "ctok_bpe_trainer_count": (ctypes.c_int, [_p, _p, _p, _u64]),
+    "ctok_bpe_trainer_train": (ctypes.c_int, [_p, _p, _p, _u64]),
+    "ctok_bpe_trainer_train_words": (ctypes.c_int, [_p, _p, _p, _p, _u64]),
+    "ctok_bpe_trainer_vocab_size": (_u64, [_p]),
+    "ctok_bpe_trainer_num_merges": (_u64, [_p]),
+    "ctok_bpe_trainer_result": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings), ctypes.POINTER(_u32p),
+                                               ctypes.POINTER(BpeStrings)]),
+    "ctok_bpe_trainer_word_counts": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings), ctypes.POINTER(_u32p)]),
+    "ctok_bpe_trainer_stats": (ctypes.c_int, [_p, ctypes.POINTER(BpeTrainerStats)]),
+    "ctok_bpe_trainer_symbols": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings)]),
+    "ctok_bpe_trainer_pair_counts": (ctypes.c_int, [_p, ctypes.POINTER(_u32p), ctypes.POINTER(_u32p),
+                                                    ctypes.POINTER(ctypes.POINTER(ctypes.c_int64)), _u64p]),
 }
 
 for _name, (_res, _args) in SIGS.items():

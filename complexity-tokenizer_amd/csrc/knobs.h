@@ -1,5 +1,5 @@
 // Every CTOK_* environment variable the library reads, gathered by the time it is read.
-// Host-only.  (The trainer's own variables are in trainer_host.cpp.)
+// Host-only.  (The INL trainer's own variables are in trainer_host.cpp.)
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -77,6 +77,14 @@ struct CallKnobs {
   bool mid512 = env_set("CTOK_MID512");
   int overlap = env_int("CTOK_OVERLAP", ctok_dev::kOverlapDefault);  // >= 1: merge passes on the idle side stream
   bool wire32 = env_set("CTOK_WIRE32");
+};
+
+// Read by every training call of the classic BPE trainer (bpe_train_host.cpp; the tests flip them
+// within one process).  Its counting also reads the INL trainer's CTOK_TRAIN_CHUNK_BYTES and
+// CTOK_TRAIN_COUNT_SLOTS.
+struct BpeTrainKnobs {
+  std::optional<uint64_t> slots = env_u64("CTOK_BPE_TRAIN_SLOTS");  // cap of the pair table's capacity
+  bool recount = env_int("CTOK_BPE_TRAIN_RECOUNT", 0) != 0;         // count all pairs again before every merge
 };
 
 }  // namespace ctok_rt

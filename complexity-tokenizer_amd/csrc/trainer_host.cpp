@@ -33,50 +33,17 @@
 
 #include "../../include/ctok_trainer.h"
 #include "host_common.h"
+#include "train_host_common.h"
 #include "trainer_internal.h"
 #include "wordcount_internal.h"
 
 using namespace ctok_train;
 using ctok_host::throw_error;
-
-#define HIPT(x)                                                                                         \
-  do {                                                                                                  \
-    hipError_t e_ = (x);                                                                                \
-    if (e_ != hipSuccess) throw_error(CTOK_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+using ctok_train_host::DBuf;
+using ctok_train_host::now_ms;
+using ctok_train_host::utf8_of;
 
 namespace {
-
-template <typename T>
-struct DBuf {  // device buffer, grown on demand
-  T* p = nullptr;
-  size_t cap = 0;
-  void ensure(size_t n) {
-    if (n <= cap) return;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIPT(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)));
-    cap = n;
-  }
-  // ensure() that reports an allocation failure instead of throwing (the buffer is then empty)
-  bool try_ensure(size_t n) {
-    if (n <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();  // (the failure is handled: leave no error behind for the next call)
-      p = nullptr;
-      return false;
-    }
-    cap = n;
-    return true;
-  }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
 
 // GPT-2 bytes_to_unicode (src/pretokenizers.rs:130-153, src/trainer.rs:20-44): byte -> code point
 std::vector<uint32_t> byte_cps() {
@@ -87,15 +54,6 @@ std::vector<uint32_t> byte_cps() {
     cp[b] = keep ? (uint32_t)b : 256u + (uint32_t)n++;
   }
   return cp;
-}
-
-std::string utf8_of(uint32_t c) {
-  std::string s;
-  if (c < 0x80) s += (char)c;
-  else if (c < 0x800) { s += (char)(0xC0 | (c >> 6)); s += (char)(0x80 | (c & 63)); }
-  else if (c < 0x10000) { s += (char)(0xE0 | (c >> 12)); s += (char)(0x80 | ((c >> 6) & 63)); s += (char)(0x80 | (c & 63)); }
-  else { s += (char)(0xF0 | (c >> 18)); s += (char)(0x80 | ((c >> 12) & 63)); s += (char)(0x80 | ((c >> 6) & 63)); s += (char)(0x80 | (c & 63)); }
-  return s;
 }
 
 // serde_json string escaping (only '"', '\\' and control characters)
@@ -117,10 +75,6 @@ void json_str(std::string& o, const std::string& s) {
     }
   }
   o += '"';
-}
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 }  // namespace
