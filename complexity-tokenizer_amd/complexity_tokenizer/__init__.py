@@ -24,8 +24,8 @@ from . import _native as _n
 from . import _fast  # the Python-object edges of encode_batch (csrc/pyfast.c); built with libctok.so
 
 __version__ = "0.3.3"
-__all__ = ["Tokenizer", "Trainer", "BpeTrainer", "Encoding", "BatchEncoding", "PanicException", "UnsupportedConfigError",
-           "DeviceError", "__version__"]
+__all__ = ["Tokenizer", "Trainer", "BpeTrainer", "WordPieceTrainer", "WordPieceModel", "Encoding", "BatchEncoding",
+           "PanicException", "UnsupportedConfigError", "DeviceError", "__version__"]
 
 
 class PanicException(BaseException):
@@ -155,6 +155,7 @@ def _split_lists(flat: np.ndarray, off: np.ndarray) -> list:
 from .encoding import BatchEncoding, Encoding  # noqa: E402
 from .trainer import Trainer  # noqa: E402
 from .bpe_trainer import BpeTrainer  # noqa: E402
+from .wordpiece import WordPieceModel, WordPieceTrainer  # noqa: E402
 
 
 class Tokenizer:

@@ -153,6 +153,21 @@ class BpeTrainerStats(ctypes.Structure):  # include/ctok_bpe_trainer.h ctok_bpe_
                [(k, ctypes.c_double) for k in ("ms_count", "ms_pairs", "ms_best", "ms_merges", "ms_host")]
 
 
+class WpTrainerConfig(ctypes.Structure):  # include/ctok_wordpiece.h
+    _fields_ = [("vocab_size", ctypes.c_uint64), ("min_frequency", ctypes.c_uint32),
+                ("special", ctypes.c_char_p), ("special_off", ctypes.POINTER(ctypes.c_uint64)),
+                ("n_special", ctypes.c_uint64), ("continuing_subword_prefix", ctypes.c_char_p),
+                ("max_input_chars_per_word", ctypes.c_uint64), ("device", ctypes.c_int)]
+
+
+class WpTrainerStats(ctypes.Structure):  # include/ctok_wordpiece.h ctok_wp_trainer_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("words", "unique_words", "initial_vocab", "merges", "table_capacity",
+                                               "rebuilds", "walked_words", "chunks", "host_chunks", "rerun_chunks",
+                                               "lowered_chunks")] + \
+               [(k, ctypes.c_double) for k in ("ms_count", "ms_match", "ms_pairs", "ms_add", "ms_walk", "ms_best",
+                                               "ms_host")]
+
+
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -228,6 +243,27 @@ SIGS = {
     "ctok_bpe_trainer_symbols": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings)]),
     "ctok_bpe_trainer_pair_counts": (ctypes.c_int, [_p, ctypes.POINTER(_u32p), ctypes.POINTER(_u32p),
                                                     ctypes.POINTER(ctypes.POINTER(ctypes.c_int64)), _u64p]),
+    # include/ctok_wordpiece.h
+    "ctok_wp_trainer_create": (ctypes.c_int, [ctypes.POINTER(WpTrainerConfig), ctypes.POINTER(_p)]),
+    "ctok_wp_trainer_destroy": (None, [_p]),
+    "ctok_wp_trainer_count": (ctypes.c_int, [_p, _p, _p, _u64]),
+    "ctok_wp_trainer_train": (ctypes.c_int, [_p, _p, _p, _u64]),
+    "ctok_wp_trainer_train_words": (ctypes.c_int, [_p, _p, _p, _p, _u64]),
+    "ctok_wp_trainer_vocab_size": (_u64, [_p]),
+    "ctok_wp_trainer_result": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings), ctypes.POINTER(_u32p),
+                                              ctypes.POINTER(BpeStrings)]),
+    "ctok_wp_trainer_word_counts": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings), ctypes.POINTER(_u32p)]),
+    "ctok_wp_trainer_tokens": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings), ctypes.POINTER(BpeStrings),
+                                              ctypes.POINTER(_u64p)]),
+    "ctok_wp_trainer_stats": (ctypes.c_int, [_p, ctypes.POINTER(WpTrainerStats)]),
+    "ctok_wp_trainer_pair_counts": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings), ctypes.POINTER(BpeStrings),
+                                                   ctypes.POINTER(ctypes.POINTER(ctypes.c_int64))]),
+    "ctok_wp_model_create": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.c_char_p, ctypes.c_char_p, _u64, ctypes.c_int,
+                                            ctypes.POINTER(_p)]),
+    "ctok_wp_model_destroy": (None, [_p]),
+    "ctok_wp_model_vocab_size": (_u64, [_p]),
+    "ctok_wp_model_encode_batch": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.POINTER(_u32p), ctypes.POINTER(_u64p)]),
+    "ctok_lowercase": (ctypes.c_int, [_p, _p, _u64, ctypes.c_int, _p, _u64, _p]),
 }
 
 for _name, (_res, _args) in SIGS.items():

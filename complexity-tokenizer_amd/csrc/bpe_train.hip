@@ -23,6 +23,7 @@
 
 #include "bpe_train_internal.h"
 #include "pair_best_hd.h"
+#include "pair_table_dev.h"
 #include "ws_split_hd.h"
 
 namespace ctok_bpe {
@@ -53,35 +54,7 @@ __global__ __launch_bounds__(kThreads) void k_ws_doc_starts(const uint64_t* doc_
   }
 }
 
-// ---- the resident pair table -----------------------------------------------------------------------
-
-__device__ __forceinline__ uint32_t slot_of(uint64_t key, uint32_t cap) {
-  const uint64_t h = (key * 0x9E3779B97F4A7C15ull) >> 32;  // 32 hash bits -> [0, cap)
-  return (uint32_t)((h * cap) >> 32);
-}
-
-// count += v for key (inserting it on first use); at most min(cap, kMaxProbe) slots are looked at
-__device__ __forceinline__ void table_add(const Table& T, uint64_t key, int64_t v) {
-  uint32_t h = slot_of(key, T.cap);
-  const uint32_t tries = T.cap < kMaxProbe ? T.cap : kMaxProbe;
-  for (uint32_t i = 0; i < tries; i++) {
-    // (a stale read can only show kEmptyKey for a taken slot: the swap below then returns its key)
-    uint64_t k = T.keys[h];
-    if (k == kEmptyKey) {
-      k = atomicCAS((unsigned long long*)&T.keys[h], (unsigned long long)kEmptyKey, (unsigned long long)key);
-      if (k == kEmptyKey) {  // this thread took the slot
-        atomicAdd(&T.ctr[kCtrTaken], 1u);
-        k = key;
-      }
-    }
-    if (k == key) {
-      atomicAdd((unsigned long long*)&T.vals[h], (unsigned long long)v);
-      return;
-    }
-    h = h + 1 == T.cap ? 0 : h + 1;
-  }
-  atomicOr(&T.ctr[kCtrOverflow], 1u);
-}
+// ---- the resident pair table (its exact add, table_add: pair_table_dev.h) ---------------------------
 
 // count_pairs: thread per word (grid-stride)
 __global__ __launch_bounds__(kThreads) void k_pair_count(Words W, Table T) {

@@ -87,4 +87,10 @@ struct BpeTrainKnobs {
   bool recount = env_int("CTOK_BPE_TRAIN_RECOUNT", 0) != 0;         // count all pairs again before every merge
 };
 
+// Read by every training call of the WordPiece trainer (wordpiece_host.cpp).  Its pair table also
+// reads BpeTrainKnobs::slots, its counting CTOK_TRAIN_CHUNK_BYTES and CTOK_TRAIN_COUNT_SLOTS.
+struct WpTrainKnobs {
+  bool recount = env_int("CTOK_WP_TRAIN_RECOUNT", 0) != 0;  // walk every word and count all pairs again in every round
+};
+
 }  // namespace ctok_rt
