@@ -24,8 +24,8 @@ from . import _native as _n
 from . import _fast  # the Python-object edges of encode_batch (csrc/pyfast.c); built with libctok.so
 
 __version__ = "0.3.3"
-__all__ = ["Tokenizer", "Trainer", "BpeTrainer", "WordPieceTrainer", "WordPieceModel", "Encoding", "BatchEncoding",
-           "PanicException", "UnsupportedConfigError", "DeviceError", "__version__"]
+__all__ = ["Tokenizer", "Trainer", "BpeTrainer", "WordPieceTrainer", "WordPieceModel", "UnigramTrainer", "UnigramModel", "Encoding",
+           "BatchEncoding", "PanicException", "UnsupportedConfigError", "DeviceError", "__version__"]
 
 
 class PanicException(BaseException):
@@ -156,6 +156,7 @@ from .encoding import BatchEncoding, Encoding  # noqa: E402
 from .trainer import Trainer  # noqa: E402
 from .bpe_trainer import BpeTrainer  # noqa: E402
 from .wordpiece import WordPieceModel, WordPieceTrainer  # noqa: E402
+from .unigram import UnigramModel, UnigramTrainer  # noqa: E402
 
 
 class Tokenizer:

@@ -168,10 +168,25 @@ class WpTrainerStats(ctypes.Structure):  # include/ctok_wordpiece.h ctok_wp_trai
                                                "ms_host")]
 
 
+class UniTrainerConfig(ctypes.Structure):  # include/ctok_unigram.h
+    _fields_ = [("vocab_size", ctypes.c_uint64), ("special", ctypes.c_char_p),
+                ("special_off", ctypes.POINTER(ctypes.c_uint64)), ("n_special", ctypes.c_uint64),
+                ("initial_vocab_size", ctypes.c_uint64), ("shrinking_factor", ctypes.c_double),
+                ("n_iterations", ctypes.c_uint64), ("max_piece_length", ctypes.c_uint64), ("device", ctypes.c_int)]
+
+
+class UniTrainerStats(ctypes.Structure):  # include/ctok_unigram.h ctok_uni_trainer_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("sentences", "chars", "seed_vocab", "iterations")] + \
+               [("vocab_sizes", ctypes.POINTER(ctypes.c_uint64))] + \
+               [(k, ctypes.c_uint64) for k in ("window", "table_capacity", "chunks", "rerun_chunks")] + \
+               [(k, ctypes.c_double) for k in ("ms_text", "ms_count", "ms_lattice", "ms_viterbi", "ms_host")]
+
+
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
+_f64p = ctypes.POINTER(ctypes.c_double)
 _sz = ctypes.c_size_t
 
 SIGS = {
@@ -264,6 +279,21 @@ SIGS = {
     "ctok_wp_model_vocab_size": (_u64, [_p]),
     "ctok_wp_model_encode_batch": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.POINTER(_u32p), ctypes.POINTER(_u64p)]),
     "ctok_lowercase": (ctypes.c_int, [_p, _p, _u64, ctypes.c_int, _p, _u64, _p]),
+    # include/ctok_unigram.h
+    "ctok_uni_trainer_create": (ctypes.c_int, [ctypes.POINTER(UniTrainerConfig), ctypes.POINTER(_p)]),
+    "ctok_uni_trainer_destroy": (None, [_p]),
+    "ctok_uni_trainer_train": (ctypes.c_int, [_p, _p, _p, _u64]),
+    "ctok_uni_trainer_train_sentences": (ctypes.c_int, [_p, _p, _p, _u64]),
+    "ctok_uni_trainer_vocab_size": (_u64, [_p]),
+    "ctok_uni_trainer_result": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings), ctypes.POINTER(_f64p)]),
+    "ctok_uni_trainer_sentences": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings)]),
+    "ctok_uni_trainer_substring_counts": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings), ctypes.POINTER(_u64p)]),
+    "ctok_uni_trainer_expected_counts": (ctypes.c_int, [_p, ctypes.POINTER(BpeStrings), ctypes.POINTER(_u64p)]),
+    "ctok_uni_trainer_stats": (ctypes.c_int, [_p, ctypes.POINTER(UniTrainerStats)]),
+    "ctok_uni_model_create": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(_p)]),
+    "ctok_uni_model_destroy": (None, [_p]),
+    "ctok_uni_model_vocab_size": (_u64, [_p]),
+    "ctok_uni_model_encode_batch": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.POINTER(_u32p), ctypes.POINTER(_u64p)]),
 }
 
 for _name, (_res, _args) in SIGS.items():
