@@ -24,7 +24,8 @@ from . import _native as _n
 from . import _fast  # the Python-object edges of encode_batch (csrc/pyfast.c); built with libctok.so
 
 __version__ = "0.3.3"
-__all__ = ["Tokenizer", "Trainer", "BpeTrainer", "WordPieceTrainer", "WordPieceModel", "UnigramTrainer", "UnigramModel", "Encoding",
+__all__ = ["Tokenizer", "Trainer", "BpeTrainer", "WordPieceTrainer", "WordPieceModel", "UnigramTrainer", "UnigramModel", "WordLevelModel",
+           "CharBpeModel", "ByteLevelBpeModel", "Encoding",
            "BatchEncoding", "PanicException", "UnsupportedConfigError", "DeviceError", "__version__"]
 
 
@@ -157,6 +158,7 @@ from .trainer import Trainer  # noqa: E402
 from .bpe_trainer import BpeTrainer  # noqa: E402
 from .wordpiece import WordPieceModel, WordPieceTrainer  # noqa: E402
 from .unigram import UnigramModel, UnigramTrainer  # noqa: E402
+from .models import ByteLevelBpeModel, CharBpeModel, WordLevelModel  # noqa: E402
 
 
 class Tokenizer:

@@ -294,6 +294,24 @@ SIGS = {
     "ctok_uni_model_destroy": (None, [_p]),
     "ctok_uni_model_vocab_size": (_u64, [_p]),
     "ctok_uni_model_encode_batch": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.POINTER(_u32p), ctypes.POINTER(_u64p)]),
+    # include/ctok_models.h
+    "ctok_wl_model_create": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(_p)]),
+    "ctok_cbpe_model_create": (ctypes.c_int, [_p, _p, _p, _u64, _p, _p, _u64, ctypes.c_char_p, ctypes.c_char_p,
+                                              ctypes.c_int, ctypes.POINTER(_p)]),
+    "ctok_blbpe_model_create": (ctypes.c_int, [_p, _p, _p, _u64, _p, _p, _u64, ctypes.c_char_p, ctypes.c_int,
+                                               ctypes.c_int, ctypes.POINTER(_p)]),
+    "ctok_wl_model_destroy": (None, [_p]),
+    "ctok_cbpe_model_destroy": (None, [_p]),
+    "ctok_blbpe_model_destroy": (None, [_p]),
+    "ctok_wl_model_vocab_size": (_u64, [_p]),
+    "ctok_cbpe_model_vocab_size": (_u64, [_p]),
+    "ctok_blbpe_model_vocab_size": (_u64, [_p]),
+    "ctok_wl_model_encode_batch": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.POINTER(_u32p), ctypes.POINTER(_u64p)]),
+    "ctok_cbpe_model_encode_batch": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.POINTER(_u32p), ctypes.POINTER(_u64p)]),
+    "ctok_blbpe_model_encode_batch": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.POINTER(_u32p), ctypes.POINTER(_u64p)]),
+    "ctok_models_limits": (None, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                  ctypes.POINTER(ctypes.c_uint64)]),
+    "ctok_models_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double)]),
 }
 
 for _name, (_res, _args) in SIGS.items():
