@@ -1,11 +1,11 @@
 // Piece-start predicate of GPT2_PATTERN on one 64-byte word per lane (k_segment), shared with
 // the host-side check in tests (tools/seg_lane_check.cpp): plain integer code, no intrinsics
-// except the 32x32->64 high multiply.
+// except the four-term byte dot product (dot4), which has a host twin.
 //
 // A word's bytes become 64-bit masks (bit i = byte i) of the code-point classes White_Space /
 // letter / number, of ' ' and '\'', and of the contraction letters, via SWAR tests on 4-byte
 // words: every test leaves its answer in bit 7 of each byte, and pack8 gathers the bit-7s of two
-// dwords into 8 mask bits with one high multiply.  Non-ASCII bytes are cleared from the ASCII
+// dwords into 8 mask bits with two byte dot products.  Non-ASCII bytes are cleared from the ASCII
 // masks and classified per code point by the caller (continuation bytes take their lead's
 // class).  The predicate itself is then a few dozen 64-bit ops on the
 // word's masks and its neighbours' (one word before and after: carried across lanes).
@@ -23,20 +23,27 @@ namespace seg {
 constexpr uint32_t kHi = 0x80808080u;
 constexpr uint32_t rep(uint32_t c) { return c * 0x01010101u; }
 
-SEG_HD uint32_t mulhi(uint32_t a, uint32_t b) {
+// a.b over the four bytes of a and b, plus c (v_dot4_u32_u8: full rate, where a 32-bit multiply
+// is quarter rate; no saturation)
+SEG_HD uint32_t dot4(uint32_t a, uint32_t b, uint32_t c) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  return __umulhi(a, b);
+  return __builtin_amdgcn_udot4(a, b, c, false);
 #else
-  return (uint32_t)(((uint64_t)a * b) >> 32);
+  for (int k = 0; k < 32; k += 8) c += ((a >> k) & 255u) * ((b >> k) & 255u);
+  return c;
 #endif
 }
 
-// bit 7 of each byte of r0 then r1 -> 8 bits (byte order).  ((r0 & hi) >> 4) | (r1 & hi) puts
-// the eight flags at bits 3,11,19,27 (r0) and 7,15,23,31 (r1); the multiplier's four terms move
-// them to bits 32..39 with no two partial products on the same bit (so no carries).
-SEG_HD uint32_t pack8(uint32_t r0, uint32_t r1) {
-  const uint32_t c = ((r0 & kHi) >> 4) | (r1 & kHi);
-  return mulhi(c, 0x20408100u) & 0xFFu;
+// bit 7 of each byte of r0 then r1 -> 8 bits (byte order), at bits 7..14: every flag byte is 0 or
+// 0x80, and the weights 1, 2, 4 .. 128 give each flag a bit of its own (so no carries).
+SEG_HD uint32_t pack8_hi(uint32_t r0, uint32_t r1) {
+  return dot4(r1 & kHi, 0x80402010u, dot4(r0 & kHi, 0x08040201u, 0u));
+}
+SEG_HD uint32_t pack8(uint32_t r0, uint32_t r1) { return pack8_hi(r0, r1) >> 7; }
+// pack8(r0, r1) << sh for sh = 0, 8, 16, 24 in one shift (the low 7 bits of pack8_hi are zero)
+SEG_HD uint32_t pack8_at(uint32_t r0, uint32_t r1, int sh) {
+  const uint32_t v = pack8_hi(r0, r1);
+  return sh >= 7 ? v << (sh - 7) : v >> (7 - sh);
 }
 
 // x7 = x & 0x7f7f7f7f.  Bit 7 of a byte is set iff the byte != c (c < 0x80).
@@ -66,12 +73,12 @@ SEG_HD Masks ascii_masks(const uint32_t (&x)[16]) {
     const uint32_t a80 = a | kHi, b80 = b | kHi;
     const int h = p >> 2, sh = 8 * (p & 3);
     // ' ' and '\'' come out inverted (bit set = not equal); flipped once per mask below
-    s[h] |= pack8(ne7(a7, ' '), ne7(b7, ' ')) << sh;
-    q[h] |= pack8(ne7(a7, '\''), ne7(b7, '\'')) << sh;
-    w[h] |= pack8(in80(a80, 9, 13), in80(b80, 9, 13)) << sh;
-    l[h] |= pack8(in80(a80 | rep(0x20), 'a', 'z'), in80(b80 | rep(0x20), 'a', 'z')) << sh;
-    n[h] |= pack8(in80(a80, '0', '9'), in80(b80, '0', '9')) << sh;
-    na[h] |= pack8(a, b) << sh;
+    s[h] |= pack8_at(ne7(a7, ' '), ne7(b7, ' '), sh);
+    q[h] |= pack8_at(ne7(a7, '\''), ne7(b7, '\''), sh);
+    w[h] |= pack8_at(in80(a80, 9, 13), in80(b80, 9, 13), sh);
+    l[h] |= pack8_at(in80(a80 | rep(0x20), 'a', 'z'), in80(b80 | rep(0x20), 'a', 'z'), sh);
+    n[h] |= pack8_at(in80(a80, '0', '9'), in80(b80, '0', '9'), sh);
+    na[h] |= pack8_at(a, b, sh);
   }
   Masks m;
   m.NA = (uint64_t)na[0] | ((uint64_t)na[1] << 32);
@@ -90,12 +97,12 @@ SEG_HD Letters letter_masks(const uint32_t (&x)[16], uint64_t na) {
     const uint32_t a7 = x[2 * p] & 0x7F7F7F7Fu, b7 = x[2 * p + 1] & 0x7F7F7F7Fu;
     const int h = p >> 2, sh = 8 * (p & 3);
     // s|t|m|d: bit 7 clear in all four "not equal" tests
-    t1[h] |= pack8(ne7(a7, 's') & ne7(a7, 't') & ne7(a7, 'm') & ne7(a7, 'd'),
-                   ne7(b7, 's') & ne7(b7, 't') & ne7(b7, 'm') & ne7(b7, 'd')) << sh;
-    r[h] |= pack8(ne7(a7, 'r'), ne7(b7, 'r')) << sh;
-    e[h] |= pack8(ne7(a7, 'e'), ne7(b7, 'e')) << sh;
-    v[h] |= pack8(ne7(a7, 'v'), ne7(b7, 'v')) << sh;
-    ll[h] |= pack8(ne7(a7, 'l'), ne7(b7, 'l')) << sh;
+    t1[h] |= pack8_at(ne7(a7, 's') & ne7(a7, 't') & ne7(a7, 'm') & ne7(a7, 'd'),
+                      ne7(b7, 's') & ne7(b7, 't') & ne7(b7, 'm') & ne7(b7, 'd'), sh);
+    r[h] |= pack8_at(ne7(a7, 'r'), ne7(b7, 'r'), sh);
+    e[h] |= pack8_at(ne7(a7, 'e'), ne7(b7, 'e'), sh);
+    v[h] |= pack8_at(ne7(a7, 'v'), ne7(b7, 'v'), sh);
+    ll[h] |= pack8_at(ne7(a7, 'l'), ne7(b7, 'l'), sh);
   }
   auto inv = [&](const uint32_t (&y)[2]) { return ~((uint64_t)y[0] | ((uint64_t)y[1] << 32)) & ~na; };
   return Letters{inv(t1), inv(r), inv(e), inv(v), inv(ll)};

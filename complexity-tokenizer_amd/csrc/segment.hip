@@ -26,6 +26,7 @@
 // classes {White_Space, L, N, other} (derivation in DESIGN.md), bit-parallel on 64-bit masks.
 #include "dev_common.h"
 #include "seg_lane.h"
+#include "seg_route_hd.h"
 
 namespace ctok_dev {
 
@@ -148,14 +149,16 @@ __device__ __forceinline__ uint32_t select_bit(uint64_t x, uint32_t k) {
 // are the tile's words, lane 63 is the next tile's first word (look-ahead: where the tile's last
 // piece ends; its bits 62-63 depend on a word no lane holds and are not used).
 //  A. per lane: the word's class / byte masks by SWAR tests (csrc/seg_lane.h); non-ASCII code
-//     points classified per code point; doc starts from the doc bitmap;
+//     points classified per code point; doc starts from the documents' offsets;
 //  B. per lane: the piece-start predicate, the neighbouring words' masks by cross-lane shuffles;
+//     then the doc-start bits by piece number (pdoc), once per tile, from each word's D & st;
 //  C. thread per piece (piece j = the j-th start of the tile): length from the next start, then
 //     routing: a piece of <= 8 bytes that is one self-encoding vocab token is finished here with
 //     one whole-piece probe; every other piece is appended to its tile's class list (<= 8 B,
 //     9..16 B, 17..32 B) or to the long list, so that the merge passes run dense, length-uniform
 //     waves.  A round is kSegUnroll slots of 64 pieces; the round's merged pieces are compacted
 //     in LDS and appended once per round (C4 k_segment 2.64 -> 2.52 ms, profiles/seg_routing/).
+//     (The mask gathers on dot products and pdoc once per tile: 2.52 -> 2.38 ms, profiles/seg_front/.)
 // (amdgpu_waves_per_eu(7): at most 72 VGPRs, 7 waves per SIMD; without it the compiler takes 72-73
 // and this kernel runs at 6-7; C4 k_segment 2.78 -> 2.67 ms, 8 waves spill: 2.96 ms,
 // profiles/r03/v30_ab_seg_waves_per_eu.txt)
@@ -233,6 +236,9 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
     ys0 = w.doc_off[dfirst + lane + 1];
   }
   seg::Masks m = seg::ascii_masks(x);
+  // the masks are complete here: their gathers must not sink below the doc-start block, away from
+  // the tests that feed them (96 flag dwords would then be live at once and spill)
+  asm volatile("" : "+v"(m.W), "+v"(m.L), "+v"(m.N), "+v"(m.S), "+v"(m.Q), "+v"(m.NA));
   {  // doc-start bits of the 64 words [base, base + 4096): the non-empty documents starting there,
      // from the tile's first document on (k_tilefirst), 64 at a time (C4: one round)
     uint64_t* s_D = s_D_all[wid];
@@ -266,7 +272,6 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
     else if (x0 >= (int64_t)B) D = ~0ull;
     else D = s_D[lane] | ~valid;
   }
-  s_D_all[wid][lane] = D;
   // every lane's word in LDS: the tile's bytes (and the look-ahead word) for the whole-piece
   // probes (s_text: the tile's first byte), the context word too for the code point decoding below
   uint32_t* s_all = s_text_all[wid] + 4;  // (s_all[-1]: the 4 bytes before the context word)
@@ -441,6 +446,24 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
   const uint64_t stw = (!first && !last) ? st : 0ull;
   const uint32_t prew = inc - c;
   uint32_t wcur = 1;  // the first word lane that can hold the next window's first piece (wave-uniform)
+  uint32_t* pdoc = w.pdoc + (size_t)tile * (kTileSlots / 32);
+  {  // pdoc, bit j: piece j starts a document.  Each word lane ORs its doc starts' piece numbers
+     // (about one start in 36 on C4) into a bitmap of kTileSlots bits, which the wave stores in one
+     // coalesced pass.  The bitmap lies over s_D, dead since every lane holds its D.
+    static_assert(kTileSlots == 64 * 64, "the pdoc bitmap of a tile: s_D's 64 u64 words");
+    // (its own address arithmetic: phase A's &s_D[lane], kept alive down to here, was spilled)
+    uint32_t dl = lane;
+    asm volatile("" : "+v"(dl));
+    uint64_t* s_doc = s_D_all[wid];
+    s_doc[dl] = 0;
+    seg_wave_sync();
+    seg::doc_pieces(stw, D, prew, [&](uint32_t j) { atomicOr((uint32_t*)s_doc + (j >> 5), 1u << (j & 31)); });
+    seg_wave_sync();
+    if (lane * 64 < np) {
+      const uint64_t dm = s_doc[dl];
+      *reinterpret_cast<uint2*>(pdoc + 2 * lane) = make_uint2((uint32_t)dm, (uint32_t)(dm >> 32));
+    }
+  }
 
   SEG_STAMP(3);
   // ---- C: thread per piece, kSegUnroll pieces per lane per round with their LDS lookups and
@@ -448,7 +471,6 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
   const bool generic = t.n_at != 0;  // added tokens can match inside pieces: no whole-piece shortcut
   using RecT = typename std::conditional<R16, uint16_t, uint32_t>::type;
   RecT* prec = (RecT*)w.prec + (size_t)tile * kTileSlots;
-  uint32_t* pdoc = w.pdoc + (size_t)tile * (kTileSlots / 32);
   uint32_t nm = 0;  // merged pieces so far (wave-uniform): the next ordinal
   uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;  // class-list lengths (wave-uniform)
   uint32_t nlong = 0;  // long pieces staged in s_long_all (wave-uniform)
@@ -556,17 +578,15 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
 
     if (lane == 0 && np <= j0 + W) s_pos[np - j0] = (uint16_t)tile_end;
     seg_wave_sync();
-    uint32_t sl[U], n[U], cls[U], plo[U], phi[U], h[U], doc[U];
+    uint32_t sl[U], n[U], cls[U], plo[U], phi[U], h[U];
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const uint32_t j = j0 + 64 * u + lane;
       sl[u] = 0;
       n[u] = 0;
-      doc[u] = 0;
       cls[u] = 4;  // 0..2 class lists, 3 long, 4 done (or inactive), 5 probe, 6 class list 3
       if (j < np) {
         sl[u] = s_pos[64 * u + lane];
-        doc[u] = (uint32_t)(s_D_all[wid][(sl[u] >> 6) + 1] >> (sl[u] & 63)) & 1u;
         const uint32_t el = s_pos[64 * u + lane + 1];
         if (el == 0xFFFFu || el - sl[u] > (generic ? (uint32_t)kShortMax : (uint32_t)kMedMax)) {
           cls[u] = 3;
@@ -575,15 +595,12 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
           cls[u] = generic ? 0 : n[u] > 32 ? 6 : n[u] > 16 ? 2 : n[u] > 8 ? 1 : 5;
         }
       }
-      // whole-piece probe key: the piece's raw bytes (from LDS), zero-padded to 8 (used by the
-      // probing lanes only, whose n is <= 8)
       const uint32_t a = sl[u] >> 2, sh = sl[u] & 3;
       const uint32_t d0 = s_text[a], d1 = s_text[a + 1], d2 = s_text[a + 2];
       const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, sh), w1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
       const uint32_t nn = n[u];
       plo[u] = nn >= 4 ? w0 : w0 & ((1u << (8 * nn)) - 1u);
       phi[u] = nn >= 8 ? w1 : nn <= 4 ? 0u : w1 & ((1u << (8 * (nn - 4))) - 1u);
-      // lanes without a probe read the spare empty slot past the table (one shared line)
       h[u] = cls[u] == 5 ? piece_hash(plo[u], phi[u], nn) & t.piece_mask : t.piece_mask + 1;
     }
     // all first probes in flight together (unrolled by hand: a loop over u around the probing
@@ -611,9 +628,6 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
       if (j < np) {
         prec[j] = (RecT)rec;
       }
-      const uint64_t dm = __ballot(doc[u] != 0);  // doc-start bits of the 64 pieces
-      if (lane == 0 && j0 + 64 * u < np)
-        *reinterpret_cast<uint2*>(pdoc + ((j0 + 64 * u) >> 5)) = make_uint2((uint32_t)dm, (uint32_t)(dm >> 32));
     }
     // per slot only the compaction: the piece's class marked on its start, its index within the
     // round at its ordinal within the round
