@@ -25,7 +25,7 @@ from . import _fast  # the Python-object edges of encode_batch (csrc/pyfast.c); 
 
 __version__ = "0.3.3"
 __all__ = ["Tokenizer", "Trainer", "BpeTrainer", "WordPieceTrainer", "WordPieceModel", "UnigramTrainer", "UnigramModel", "WordLevelModel",
-           "CharBpeModel", "ByteLevelBpeModel", "Encoding",
+           "CharBpeModel", "ByteLevelBpeModel", "Normalizer", "Encoding",
            "BatchEncoding", "PanicException", "UnsupportedConfigError", "DeviceError", "__version__"]
 
 
@@ -159,6 +159,7 @@ from .bpe_trainer import BpeTrainer  # noqa: E402
 from .wordpiece import WordPieceModel, WordPieceTrainer  # noqa: E402
 from .unigram import UnigramModel, UnigramTrainer  # noqa: E402
 from .models import ByteLevelBpeModel, CharBpeModel, WordLevelModel  # noqa: E402
+from .normalizers import Normalizer  # noqa: E402
 
 
 class Tokenizer:

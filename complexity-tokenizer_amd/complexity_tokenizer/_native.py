@@ -182,6 +182,15 @@ class UniTrainerStats(ctypes.Structure):  # include/ctok_unigram.h ctok_uni_trai
                [(k, ctypes.c_double) for k in ("ms_text", "ms_count", "ms_lattice", "ms_viterbi", "ms_host")]
 
 
+class NormStep(ctypes.Structure):  # include/ctok_normalizer.h ctok_norm_step
+    _fields_ = [("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("a", ctypes.c_void_p), ("a_len", ctypes.c_uint64),
+                ("b", ctypes.c_void_p), ("b_len", ctypes.c_uint64)]
+
+
+class NormInfo(ctypes.Structure):  # include/ctok_normalizer.h ctok_normalizer_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("steps", "steps_changed", "bytes_in", "bytes_out", "bytes_peak")]
+
+
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -312,6 +321,14 @@ SIGS = {
     "ctok_models_limits": (None, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
                                   ctypes.POINTER(ctypes.c_uint64)]),
     "ctok_models_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double)]),
+    # include/ctok_normalizer.h
+    "ctok_normalizer_create": (ctypes.c_int, [ctypes.POINTER(NormStep), _u64, ctypes.c_int, ctypes.POINTER(_p)]),
+    "ctok_normalizer_destroy": (None, [_p]),
+    "ctok_normalizer_run": (ctypes.c_int, [_p, _p, _p, _u64, _p, _u64, _p]),
+    "ctok_normalizer_run_device": (ctypes.c_int, [_p, _p, _p, _u64, _u64, _p, _u64, _p, _u64p, _p]),
+    "ctok_normalizer_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), _u64, _u64p]),
+    "ctok_normalizer_stage_name": (ctypes.c_char_p, [_p, _u64]),
+    "ctok_normalizer_stats": (ctypes.c_int, [_p, ctypes.POINTER(NormInfo)]),
 }
 
 for _name, (_res, _args) in SIGS.items():

@@ -31,6 +31,7 @@
 #include "host_common.h"
 #include "knobs.h"
 #include "lowercase_hd.h"
+#include "lowercase_host.h"
 #include "pair_best_hd.h"
 #include "train_host_common.h"
 #include "wordcount_internal.h"
@@ -87,22 +88,12 @@ bool starts_with(const std::string& s, const std::string& p) { return s.size() >
 
 // ---- Lowercase on the device -------------------------------------------------------------------------
 
-struct LowerBufs {
-  DBuf<uint64_t> len, tmp, out_off;
-  DBuf<uint8_t> out;
-  DBuf<uint32_t> changed;
-};
-
-struct Lowered {  // device pointers: the input's own when nothing changed
-  const uint8_t* text;
-  const uint64_t* doc_off;
-  uint64_t n_bytes;
-  bool changed;
-};
+}  // namespace
 
 // text: n_bytes > 0 device bytes of n_docs > 0 texts (doc_off[0] = 0, doc_off[n_docs] = n_bytes)
-Lowered lower_device(LowerBufs& b, const uint8_t* text, uint64_t n_bytes, const uint64_t* doc_off, uint64_t n_docs,
-                     hipStream_t s) {
+// (declared in lowercase_host.h: the Normalizer's Lowercase step uses it too)
+Lowered ctok_wp::lower_device(LowerBufs& b, const uint8_t* text, uint64_t n_bytes, const uint64_t* doc_off,
+                              uint64_t n_docs, hipStream_t s, uint64_t refuse_from) {
   const uint64_t n_spans = (n_bytes + kLowerSpan - 1) / kLowerSpan;
   b.len.ensure(n_spans + 1);
   b.changed.ensure(1);
@@ -118,12 +109,15 @@ Lowered lower_device(LowerBufs& b, const uint8_t* text, uint64_t n_bytes, const 
   HIPT(hipMemcpyAsync(&total, b.len.p + n_spans, 8, hipMemcpyDeviceToHost, s));
   HIPT(hipStreamSynchronize(s));
   if (total > n_bytes + n_bytes / 2 + 4) throw_error(CTOK_E_DEVICE, "lowercase: more output than 3/2 of the input");
+  if (total >= refuse_from) throw_error(CTOK_E_CAPACITY, "lowercase: the output reaches " + std::to_string(refuse_from) + " bytes");
   b.out.ensure(total + 16);
   b.out_off.ensure(n_docs + 1);
   HIPT(hipMemsetAsync(b.out.p + total, 0, 16, s));
   HIPT(launch_lower_write(text, n_bytes, doc_off, n_docs, b.len.p, b.out.p, b.out_off.p, s));
   return Lowered{b.out.p, b.out_off.p, total, true};
 }
+
+namespace {
 
 std::string byte_level_nfc_json() {
   // normalizer NFC with a ByteLevel pre-tokenizer (whose pieces are not used); the byte alphabet
