@@ -191,6 +191,15 @@ class NormInfo(ctypes.Structure):  # include/ctok_normalizer.h ctok_normalizer_i
     _fields_ = [(k, ctypes.c_uint64) for k in ("steps", "steps_changed", "bytes_in", "bytes_out", "bytes_peak")]
 
 
+class PretokStep(ctypes.Structure):  # include/ctok_pretokenizer.h ctok_pretok_step
+    _fields_ = [("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("a", ctypes.c_void_p), ("a_len", ctypes.c_uint64),
+                ("cp", ctypes.c_uint32)]
+
+
+class PretokInfo(ctypes.Structure):  # include/ctok_pretokenizer.h ctok_pretokenizer_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("steps", "steps_rewriting", "bytes_in", "bytes_out", "bytes_peak", "words")]
+
+
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -329,6 +338,15 @@ SIGS = {
     "ctok_normalizer_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), _u64, _u64p]),
     "ctok_normalizer_stage_name": (ctypes.c_char_p, [_p, _u64]),
     "ctok_normalizer_stats": (ctypes.c_int, [_p, ctypes.POINTER(NormInfo)]),
+    # include/ctok_pretokenizer.h
+    "ctok_pretokenizer_create": (ctypes.c_int, [ctypes.POINTER(PretokStep), _u64, ctypes.c_int, ctypes.POINTER(_p)]),
+    "ctok_pretokenizer_destroy": (None, [_p]),
+    "ctok_pretok_split_class": (ctypes.c_int, [ctypes.c_char_p, _u64]),
+    "ctok_pretokenizer_run": (ctypes.c_int, [_p, _p, _p, _u64, _p, _u64, _p, _u64, _p, _u64p, _u64p]),
+    "ctok_pretokenizer_run_device": (ctypes.c_int, [_p, _p, _p, _u64, _u64, _p, _u64, _p, _u64, _p, _u64p, _u64p, _p]),
+    "ctok_pretokenizer_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), _u64, _u64p]),
+    "ctok_pretokenizer_stage_name": (ctypes.c_char_p, [_p, _u64]),
+    "ctok_pretokenizer_stats": (ctypes.c_int, [_p, ctypes.POINTER(PretokInfo)]),
 }
 
 for _name, (_res, _args) in SIGS.items():

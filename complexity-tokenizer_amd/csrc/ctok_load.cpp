@@ -21,6 +21,7 @@
 #include "gen/unicode_data.h"
 #include "host_internal.h"
 #include "knobs.h"
+#include "rust_regex.h"
 
 namespace ctok_rt __attribute__((visibility("hidden"))) {
 
