@@ -200,6 +200,16 @@ class PretokInfo(ctypes.Structure):  # include/ctok_pretokenizer.h ctok_pretoken
     _fields_ = [(k, ctypes.c_uint64) for k in ("steps", "steps_rewriting", "bytes_in", "bytes_out", "bytes_peak", "words")]
 
 
+class DecStep(ctypes.Structure):  # include/ctok_decoder.h ctok_dec_step
+    _fields_ = [("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("a", ctypes.c_void_p), ("a_len", ctypes.c_uint64),
+                ("b", ctypes.c_void_p), ("b_len", ctypes.c_uint64), ("cp", ctypes.c_uint32), ("start", ctypes.c_uint64),
+                ("stop", ctypes.c_uint64)]
+
+
+class DecInfo(ctypes.Structure):  # include/ctok_decoder.h ctok_decoder_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("steps", "passes", "docs", "tokens", "bytes_in", "bytes_out", "bytes_peak")]
+
+
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -347,6 +357,17 @@ SIGS = {
     "ctok_pretokenizer_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), _u64, _u64p]),
     "ctok_pretokenizer_stage_name": (ctypes.c_char_p, [_p, _u64]),
     "ctok_pretokenizer_stats": (ctypes.c_int, [_p, ctypes.POINTER(PretokInfo)]),
+    # include/ctok_decoder.h
+    "ctok_decoder_create": (ctypes.c_int, [ctypes.POINTER(DecStep), _u64, ctypes.c_int, ctypes.POINTER(_p)]),
+    "ctok_decoder_destroy": (None, [_p]),
+    "ctok_decoder_set_vocab": (ctypes.c_int, [_p, _p, _u64, _p, _p, _u64]),
+    "ctok_decoder_run": (ctypes.c_int, [_p, _p, _p, _p, _u64, _p, _u64, _p, _u64p]),
+    "ctok_decoder_run_ids": (ctypes.c_int, [_p, _p, _p, _u64, _p, _u64, _p, _u64p]),
+    "ctok_decoder_fetch": (ctypes.c_int, [_p, _p, _u64, _p, _u64p]),
+    "ctok_decoder_run_device": (ctypes.c_int, [_p, _p, _p, _p, _u64, _u64, _u64, _p, _u64, _p, _u64p, _p]),
+    "ctok_decoder_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), _u64, _u64p]),
+    "ctok_decoder_stage_name": (ctypes.c_char_p, [_p, _u64]),
+    "ctok_decoder_stats": (ctypes.c_int, [_p, ctypes.POINTER(DecInfo)]),
 }
 
 for _name, (_res, _args) in SIGS.items():

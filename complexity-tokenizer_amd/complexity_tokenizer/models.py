@@ -259,6 +259,17 @@ class CharBpeModel(_Model):
                 out.append(t)
         return "".join(out).rstrip(_WHITE_SPACE)
 
+    def decode_batch(self, batch) -> list:
+        """decode of every id list, in one pass over the batch on the GPU: Decoder.bpe(suffix) over the
+        model's id -> token map, bound at the first call; extension."""
+        dec = getattr(self, "_decoder", None)
+        if dec is None:
+            from .decoders import Decoder
+            dec = Decoder.bpe(self._suffix, device=self.device)
+            dec.set_vocab(self._vocab_r)
+            self._decoder = dec
+        return dec.decode_ids_batch(batch)
+
 
 class ByteLevelBpeModel(_Model):
     """ByteLevelBpeModel(vocab, merges, unk_token="<unk>", add_prefix_space=True) --

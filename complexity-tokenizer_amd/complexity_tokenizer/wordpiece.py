@@ -142,6 +142,17 @@ class WordPieceModel:
             empty = empty and not token
         return "".join(result)
 
+    def decode_batch(self, batch) -> list:
+        """decode of every id list, in one pass over the batch on the GPU: Decoder.wordpiece(prefix,
+        cleanup=False) over the model's id -> token map, bound at the first call; extension."""
+        dec = getattr(self, "_decoder", None)
+        if dec is None:
+            from .decoders import Decoder
+            dec = Decoder.wordpiece(self._prefix, cleanup=False, device=self.device)
+            dec.set_vocab(self._vocab_r)
+            self._decoder = dec
+        return dec.decode_ids_batch(batch)
+
     @property
     def vocab_size(self) -> int:
         return len(self._vocab)
