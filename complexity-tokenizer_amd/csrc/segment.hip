@@ -159,6 +159,8 @@ __device__ __forceinline__ uint32_t select_bit(uint64_t x, uint32_t k) {
 //     waves.  A round is kSegUnroll slots of 64 pieces; the round's merged pieces are compacted
 //     in LDS and appended once per round (C4 k_segment 2.64 -> 2.52 ms, profiles/seg_routing/).
 //     (The mask gathers on dot products and pdoc once per tile: 2.52 -> 2.38 ms, profiles/seg_front/.)
+//     A round with at most 128 pieces runs a body of two slots instead of four ("live slots":
+//     2.38 -> 2.16 ms, C5 1.65 -> 1.57 ms, profiles/seg_live/).
 // (amdgpu_waves_per_eu(7): at most 72 VGPRs, 7 waves per SIMD; without it the compiler takes 72-73
 // and this kernel runs at 6-7; C4 k_segment 2.78 -> 2.67 ms, 8 waves spill: 2.96 ms,
 // profiles/r03/v30_ab_seg_waves_per_eu.txt)
@@ -578,9 +580,12 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
 
     if (lane == 0 && np <= j0 + W) s_pos[np - j0] = (uint16_t)tile_end;
     seg_wave_sync();
+    // Live slots: a round with at most two slots of pieces (a C4 tile's fifth round) runs a body
+    // of two slots; it never touches slots 2 and 3 -- front, probe, record, store, mark,
+    // compaction -- so it sees nothing that the round before left in them.
+    const bool upper = uni((uint32_t)(j0 + 128 < np)) != 0;
     uint32_t sl[U], n[U], cls[U], plo[U], phi[U], h[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
+    auto front = [&](int u) __attribute__((always_inline)) {
       const uint32_t j = j0 + 64 * u + lane;
       sl[u] = 0;
       n[u] = 0;
@@ -602,44 +607,74 @@ __global__ __launch_bounds__(64 * kSegWaves) __attribute__((amdgpu_waves_per_eu(
       plo[u] = nn >= 4 ? w0 : w0 & ((1u << (8 * nn)) - 1u);
       phi[u] = nn >= 8 ? w1 : nn <= 4 ? 0u : w1 & ((1u << (8 * (nn - 4))) - 1u);
       h[u] = cls[u] == 5 ? piece_hash(plo[u], phi[u], nn) & t.piece_mask : t.piece_mask + 1;
-    }
-    // all first probes in flight together (unrolled by hand: a loop over u around the probing
-    // loop would not unroll, and the arrays would go to scratch)
+    };
+    // The slot's probe result becomes its record (hitv[u]) and its class after the probe.
+    // (written as flag arithmetic: an if / else-if chain assigning cls[u] in each arm was
+    // miscompiled by this hipcc in the unrolled loop)
     uint32_t hitv[U];
-#define CTOK_PROBE_LOAD(u) const uint4 e##u = t.piece_tab[h[u]];
-#define CTOK_PROBE_USE(u) hitv[u] = piece_probe(t, e##u, h[u], plo[u], phi[u], n[u]);
-    CTOK_PROBE_LOAD(0) CTOK_PROBE_LOAD(1) CTOK_PROBE_LOAD(2) CTOK_PROBE_LOAD(3)
-    CTOK_PROBE_USE(0) CTOK_PROBE_USE(1) CTOK_PROBE_USE(2) CTOK_PROBE_USE(3)
-#undef CTOK_PROBE_LOAD
-#undef CTOK_PROBE_USE
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const uint32_t j = j0 + 64 * u + lane;
+    auto record = [&](int u, const uint4 e) __attribute__((always_inline)) {
       uint32_t rec = kRecMerged32;  // a later pass produces the piece's ids (its mrec slot)
-      // (written as flag arithmetic: an if / else-if chain assigning cls[u] in each arm was
-      // miscompiled by this hipcc in the unrolled loop)
       if (cls[u] == 5) {
-        const bool hit = hitv[u] != kNone;
-        rec = hit ? hitv[u] : kRecMerged32;
+        const uint32_t id = piece_probe(t, e, h[u], plo[u], phi[u], n[u]);
+        const bool hit = id != kNone;
+        rec = hit ? id : kRecMerged32;
         by2h += hit ? 0x10000u : 0u;
         cls[u] = hit ? 4u : 0u;
       }
-      // every piece's record: whole coalesced lines (u16 on narrow vocabularies)
-      if (j < np) {
-        prec[j] = (RecT)rec;
-      }
+      hitv[u] = rec;
+    };
+    // every piece's record: whole coalesced lines (u16 on narrow vocabularies)
+    auto store = [&](int u) __attribute__((always_inline)) {
+      const uint32_t j = j0 + 64 * u + lane;
+      if (j < np) prec[j] = (RecT)hitv[u];
+    };
+    // Two bodies, chosen by a wave-uniform branch; the full one is the round as it was.  In each,
+    // the fronts of all its slots run together (their LDS reads overlap), then all first probes
+    // are in flight together, and each slot's record is stored as soon as it is made: a wave waits
+    // for a probe entry only where one of its lanes probes, and a slot without a probing lane never
+    // waits at all.  (Measured the other way -- one body with slots 2 and 3 under `upper`, every
+    // entry waited for at one point ahead of the stores -- C4 gained 0.11 ms more and C5 lost 0.07:
+    // profiles/seg_live/.)  (The probes are spelled out: a loop over u around the probing loop
+    // would not unroll, and the arrays would go to scratch.)
+    if (upper) {
+      front(0);
+      front(1);
+      front(2);
+      front(3);
+      const uint4 e0 = t.piece_tab[h[0]], e1 = t.piece_tab[h[1]], e2 = t.piece_tab[h[2]], e3 = t.piece_tab[h[3]];
+      record(0, e0);
+      store(0);
+      record(1, e1);
+      store(1);
+      record(2, e2);
+      store(2);
+      record(3, e3);
+      store(3);
+    } else {
+      front(0);
+      front(1);
+      const uint4 e0 = t.piece_tab[h[0]], e1 = t.piece_tab[h[1]];
+      record(0, e0);
+      store(0);
+      record(1, e1);
+      store(1);
     }
     // per slot only the compaction: the piece's class marked on its start, its index within the
     // round at its ordinal within the round
-    seg_wave_sync();  // every slot's s_pos reads before the first mark lands on them
-#pragma unroll
-    for (int u = 0; u < U; u++) {
+    auto compact = [&](int u) __attribute__((always_inline)) {
       const uint64_t mm = __ballot(cls[u] != 4);
       if (cls[u] != 4) {
         s_pos[64 * u + lane] = (uint16_t)seg_mark(sl[u], cls[u]);
         s_buf[cnt + (uint32_t)__popcll(mm & lanemask_lt())] = (uint8_t)(64 * u + lane);
       }
       cnt += (uint32_t)__popcll(mm);
+    };
+    seg_wave_sync();  // every slot's s_pos reads before the first mark lands on them
+    compact(0);
+    compact(1);
+    if (upper) {
+      compact(2);
+      compact(3);
     }
     seg_wave_sync();
     flush();
