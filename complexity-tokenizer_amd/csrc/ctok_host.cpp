@@ -46,6 +46,17 @@ struct DeviceCall {
   }
 };
 
+// The text and the ids of a device entry point (include/ctok.h, "Buffers of the device entry
+// points"): refused at the entry, before the device is looked up, so that no kernel -- k_nfc_check
+// and k_norm read the caller's text before the pipeline does -- runs on a misaligned pointer.  (The
+// library's own text buffers, norm_text and sub_text among them, are allocations and so aligned.)
+void check_device_text(const uint8_t* d_utf8, uint64_t n_bytes) {
+  if (n_bytes && ((uintptr_t)d_utf8 & 15)) throw_err(CTOK_E_ARG, "device text buffer must be 16-byte aligned");
+}
+void check_device_ids(const uint32_t* d_ids, uint64_t n_ids) {
+  if (n_ids && ((uintptr_t)d_ids & 3)) throw_err(CTOK_E_ARG, "device ids buffer must be 4-byte aligned");
+}
+
 // A host batch on the device, in pad_in_text (16 zero bytes after it) and pad_in_off
 void stage_host_batch(DeviceState* ds, const uint8_t* utf8, const uint64_t* off, uint64_t n_docs, hipStream_t s) {
   const uint64_t B = off[n_docs];
@@ -75,7 +86,6 @@ uint64_t decode_device(ctok* t, DeviceState* ds, const uint32_t* d_ids, const ui
     throw_err(CTOK_E_UNSUPPORTED, "decoder " + t->decoder_name + " is outside the ByteLevel-BPE decode path");
   if (n_ids >= 0xF0000000ull || n_docs >= 0xF0000000ull)
     throw_err(CTOK_E_ARG, "a single decode call is limited to < 3.75 G ids and docs; split the batch");
-  if (n_ids && ((uintptr_t)d_ids & 3)) throw_err(CTOK_E_ARG, "device ids buffer must be 4-byte aligned");
   ensure_decode_tables(t, ds, s);
   DecTables tb{(const uint2*)ds->dec_ent.p, (uint32_t)(t->dec_ent.size() / 2), ds->dec_bytes.p};
   DecWork w{};
@@ -530,6 +540,7 @@ int ctok_encode_batch_device(const ctok* tc, const uint8_t* d_utf8, const uint64
   ctok* t = const_cast<ctok*>(tc);
   return run([&] {
     double t0 = now_ms();
+    check_device_text(d_utf8, n_bytes);
     DeviceCall dc(t, exec);
     EncodeCall call;
     call.text = d_utf8, call.doc_off = d_doc_off, call.n_docs = n_docs, call.n_bytes = n_bytes;
@@ -548,6 +559,7 @@ int ctok_decode_batch_device(const ctok* tc, const uint32_t* d_ids, const uint64
   ctok* t = const_cast<ctok*>(tc);
   return run([&] {
     double t0 = now_ms();
+    check_device_ids(d_ids, n_ids);
     DeviceCall dc(t, exec);
     auto get_out = [&](uint64_t n) -> uint8_t* {
       if (n_bytes_out) *n_bytes_out = n;
@@ -803,6 +815,7 @@ int ctok_encode_padded_device(const ctok* tc, const uint8_t* d_utf8, const uint6
     double t0 = now_ms();
     const uint32_t f = o->flags;
     const uint64_t rows = pad_rows_of(t, o, n_docs);
+    check_device_text(d_utf8, n_bytes);
     DeviceCall dc(t, exec);
     DeviceState* ds = dc.ds;
     hipStream_t s = dc.s;
@@ -907,6 +920,7 @@ int ctok_encode_windows_device(const ctok* tc, const uint8_t* d_utf8, const uint
     po.flags |= CTOK_P_TRUNCATE | CTOK_P_WINDOWS;
     const uint32_t f = po.flags;
     const uint64_t rows = pad_rows_of(t, &po, n_docs);
+    check_device_text(d_utf8, n_bytes);
     DeviceCall dc(t, exec);
     DeviceState* ds = dc.ds;
     hipStream_t s = dc.s;

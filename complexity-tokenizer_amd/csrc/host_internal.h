@@ -328,7 +328,7 @@ enum class EncodeMode {
 
 // One encode_device call on device-resident buffers
 struct EncodeCall {
-  const uint8_t* text = nullptr;    // 16-byte aligned, 16 readable bytes past n_bytes
+  const uint8_t* text = nullptr;    // 16-byte aligned (a caller's pointer: checked at the C entry), 16 readable bytes past n_bytes, their content ignored
   const uint64_t* doc_off = nullptr;  // [n_docs + 1]
   uint64_t n_docs = 0, n_bytes = 0;
   uint32_t* ids = nullptr;          // output (null with SegmentOnly)

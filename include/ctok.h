@@ -187,9 +187,33 @@ int ctok_encode_batch(const ctok* tok, const uint8_t* utf8, const uint64_t* doc_
                       uint32_t* ids, uint64_t ids_cap, uint64_t* tok_off,
                       const ctok_exec* exec, ctok_stats* stats);
 
+/* ------------------------------------------------- buffers of the device entry points
+ * ctok_encode_batch_device, ctok_encode_padded_device, ctok_encode_windows_device (text) and
+ * ctok_decode_batch_device (ids) take device pointers.  What they ask of them
+ * (tests/test_gpu_text_tail.py pins each rule):
+ *   - Alignment.  d_utf8 must be 16-byte aligned when n_bytes > 0, and d_ids of the decode 4-byte
+ *     aligned when n_ids > 0: CTOK_E_ARG otherwise, checked at the entry, before any device is
+ *     used, so a refused call launches nothing and writes nothing.  Offsets are uint64_t arrays
+ *     and ids uint32_t arrays with their natural alignment.
+ *   - The end of the text.  The 16 bytes after the text, d_utf8[n_bytes .. n_bytes + 16), must be
+ *     readable device memory: the kernels load the aligned words that hold the text's last byte
+ *     and mask what lies past it.  What those bytes hold changes no result -- they need not be
+ *     zero, and nothing past n_bytes + 16 is read.  (The library's host entry points stage and
+ *     normalise text into buffers of their own under the same rule; a result does not depend on
+ *     what an earlier call left in them.)
+ *   - Exact capacity.  ids_cap may be exactly the number of ids: nothing past ids[n_tokens) and
+ *     tok_off[n_docs] is written.
+ *   - CTOK_E_CAPACITY from the encode.  The pipeline has run: tok_off is complete, tok_off[n_docs]
+ *     holds the number of ids needed (*n_tokens_out is not set), ids[0 .. ids_cap) hold the
+ *     first ids_cap ids, and nothing past them is written.  The padded and the windowed encode
+ *     and the decode say what they leave at their own declarations.  The handle is unaffected: the
+ *     next call is an ordinary call. */
+
 /* Same, with every buffer already resident in HBM of exec->device (device pointers) and the
  * work ordered on exec->stream.  n_bytes = doc_off[n_docs] (passed so the host need not read
- * device memory).  *n_tokens_out (host) receives the total number of ids written. */
+ * device memory).  *n_tokens_out (host) receives the total number of ids written.  Alignment, the
+ * 16 readable bytes after the text, exact ids_cap and CTOK_E_CAPACITY: "buffers of the device entry
+ * points" above. */
 int ctok_encode_batch_device(const ctok* tok, const uint8_t* d_utf8, const uint64_t* d_doc_off,
                              uint64_t n_docs, uint64_t n_bytes, uint32_t* d_ids, uint64_t ids_cap,
                              uint64_t* d_tok_off, uint64_t* n_tokens_out,
@@ -233,7 +257,9 @@ int ctok_decode_batch(const ctok* tok, const uint32_t* ids, const uint64_t* tok_
 
 /* Same, with ids / tok_off / out / out_off resident in HBM of exec->device and the work ordered
  * on exec->stream; n_ids = tok_off[n_docs].  *n_bytes_out receives the output size (also on
- * CTOK_E_CAPACITY, when out_cap is too small and nothing is written). */
+ * CTOK_E_CAPACITY, when out_cap is too small and nothing is written).  d_ids must be 4-byte
+ * aligned (CTOK_E_ARG at the entry, "buffers of the device entry points" above); no id past
+ * d_ids[n_ids) is read. */
 int ctok_decode_batch_device(const ctok* tok, const uint32_t* d_ids, const uint64_t* d_tok_off, uint64_t n_docs,
                              uint64_t n_ids, uint32_t options, uint8_t* d_out, uint64_t out_cap,
                              uint64_t* d_out_off, uint64_t* n_bytes_out, const ctok_exec* exec,
@@ -277,7 +303,10 @@ int ctok_encode_padded(const ctok* tok, const uint8_t* utf8, const uint64_t* doc
                        const ctok_pad_opts* opts, uint32_t* ids, uint32_t* attention_mask, uint32_t* type_ids,
                        uint32_t* special_mask, uint64_t cap, uint64_t* row_len, uint64_t* width_out,
                        const ctok_exec* exec, ctok_stats* stats);
-/* Same on HBM-resident buffers (device pointers, work on exec->stream); n_bytes = doc_off[n_docs]. */
+/* Same on HBM-resident buffers (device pointers, work on exec->stream); n_bytes = doc_off[n_docs].
+ * d_utf8: 16-byte aligned (CTOK_E_ARG at the entry) with 16 readable bytes after the text whose
+ * content is ignored ("buffers of the device entry points" above).  CTOK_E_CAPACITY as for
+ * ctok_encode_padded: d_row_len and *width_out filled, the arrays untouched. */
 int ctok_encode_padded_device(const ctok* tok, const uint8_t* d_utf8, const uint64_t* d_doc_off, uint64_t n_docs,
                               uint64_t n_bytes, const ctok_pad_opts* opts, uint32_t* d_ids, uint32_t* d_attention,
                               uint32_t* d_type_ids, uint32_t* d_special, uint64_t cap, uint64_t* d_row_len,
@@ -322,7 +351,10 @@ int ctok_encode_windows(const ctok* tok, const uint8_t* utf8, const uint64_t* do
                         uint32_t* type_ids, uint32_t* special_mask, uint64_t cap, uint64_t* win_len,
                         uint32_t* win_row, uint64_t* win_start, uint64_t win_cap, uint64_t* row_win,
                         uint64_t* n_windows_out, uint64_t* width_out, const ctok_exec* exec, ctok_stats* stats);
-/* Same on HBM-resident buffers (device pointers, work on exec->stream); n_bytes = doc_off[n_docs]. */
+/* Same on HBM-resident buffers (device pointers, work on exec->stream); n_bytes = doc_off[n_docs].
+ * d_utf8: 16-byte aligned (CTOK_E_ARG at the entry, after the stride check) with 16 readable
+ * bytes after the text whose content is ignored ("buffers of the device entry points" above).
+ * The window arrays may have exactly n_windows * width cells and n_windows records. */
 int ctok_encode_windows_device(const ctok* tok, const uint8_t* d_utf8, const uint64_t* d_doc_off, uint64_t n_docs,
                                uint64_t n_bytes, const ctok_pad_opts* opts, uint64_t stride, uint32_t* d_ids,
                                uint32_t* d_attention, uint32_t* d_type_ids, uint32_t* d_special, uint64_t cap,
