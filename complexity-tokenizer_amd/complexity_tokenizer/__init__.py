@@ -25,7 +25,7 @@ from . import _fast  # the Python-object edges of encode_batch (csrc/pyfast.c); 
 
 __version__ = "0.3.3"
 __all__ = ["Tokenizer", "Trainer", "BpeTrainer", "WordPieceTrainer", "WordPieceModel", "UnigramTrainer", "UnigramModel", "WordLevelModel",
-           "CharBpeModel", "ByteLevelBpeModel", "Normalizer", "PreTokenizer", "Decoder", "Encoding",
+           "CharBpeModel", "ByteLevelBpeModel", "Normalizer", "PreTokenizer", "Decoder", "PostProcessor", "Encoding",
            "BatchEncoding", "PanicException", "UnsupportedConfigError", "DeviceError", "__version__"]
 
 
@@ -162,6 +162,7 @@ from .models import ByteLevelBpeModel, CharBpeModel, WordLevelModel  # noqa: E40
 from .normalizers import Normalizer  # noqa: E402
 from .pretokenizers import PreTokenizer  # noqa: E402
 from .decoders import Decoder  # noqa: E402
+from .postprocessors import PostProcessor  # noqa: E402
 
 
 class Tokenizer:

@@ -210,6 +210,34 @@ class DecInfo(ctypes.Structure):  # include/ctok_decoder.h ctok_decoder_info
     _fields_ = [(k, ctypes.c_uint64) for k in ("steps", "passes", "docs", "tokens", "bytes_in", "bytes_out", "bytes_peak")]
 
 
+class PpStep(ctypes.Structure):  # include/ctok_postprocessor.h ctok_pp_step
+    _fields_ = [("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("single", ctypes.c_void_p), ("single_len", ctypes.c_uint64),
+                ("pair", ctypes.c_void_p), ("pair_len", ctypes.c_uint64), ("tok_bytes", ctypes.c_void_p), ("tok_off", ctypes.c_void_p),
+                ("tok_id", ctypes.c_void_p), ("n_tok", ctypes.c_uint64), ("id_a", ctypes.c_uint32), ("id_b", ctypes.c_uint32)]
+
+
+class PpBatch(ctypes.Structure):  # ctok_pp_batch
+    _fields_ = [("ids", ctypes.c_void_p), ("off", ctypes.c_void_p), ("pair_ids", ctypes.c_void_p), ("pair_off", ctypes.c_void_p),
+                ("has_pair", ctypes.c_void_p), ("n_rows", ctypes.c_uint64)]
+
+
+class PpOpts(ctypes.Structure):  # ctok_pp_opts
+    _fields_ = [("truncate", ctypes.c_uint32), ("strategy", ctypes.c_uint32), ("truncate_to", ctypes.c_uint64),
+                ("padded", ctypes.c_uint32), ("pad_left", ctypes.c_uint32), ("pad_to", ctypes.c_uint64), ("pad_id", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class PpOut(ctypes.Structure):  # ctok_pp_out
+    _fields_ = [("ids", ctypes.c_void_p), ("ids_cap", ctypes.c_uint64), ("off", ctypes.c_void_p), ("attention_mask", ctypes.c_void_p),
+                ("token_type_ids", ctypes.c_void_p), ("special_tokens_mask", ctypes.c_void_p), ("row_len", ctypes.c_void_p),
+                ("n_ids", ctypes.c_uint64), ("width", ctypes.c_uint64)]
+
+
+class PpInfo(ctypes.Structure):  # ctok_postprocessor_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("steps", "items_single", "items_pair", "rows", "ids_in", "pair_ids_in", "ids_out",
+                                               "width")]
+
+
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -368,6 +396,16 @@ SIGS = {
     "ctok_decoder_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), _u64, _u64p]),
     "ctok_decoder_stage_name": (ctypes.c_char_p, [_p, _u64]),
     "ctok_decoder_stats": (ctypes.c_int, [_p, ctypes.POINTER(DecInfo)]),
+    # include/ctok_postprocessor.h
+    "ctok_postprocessor_create": (ctypes.c_int, [ctypes.POINTER(PpStep), _u64, ctypes.c_int, ctypes.POINTER(_p)]),
+    "ctok_postprocessor_destroy": (None, [_p]),
+    "ctok_postprocessor_run": (ctypes.c_int, [_p, ctypes.POINTER(PpBatch), ctypes.POINTER(PpOpts), ctypes.POINTER(PpOut)]),
+    "ctok_postprocessor_fetch": (ctypes.c_int, [_p, ctypes.POINTER(PpOut)]),
+    "ctok_postprocessor_run_device": (ctypes.c_int, [_p, ctypes.POINTER(PpBatch), _u64, _u64, ctypes.POINTER(PpOpts), _p, _u64, _p,
+                                                     _u64p, _p]),
+    "ctok_postprocessor_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), _u64, _u64p]),
+    "ctok_postprocessor_stage_name": (ctypes.c_char_p, [_p, _u64]),
+    "ctok_postprocessor_stats": (ctypes.c_int, [_p, ctypes.POINTER(PpInfo)]),
 }
 
 for _name, (_res, _args) in SIGS.items():
