@@ -25,8 +25,8 @@ from . import _fast  # the Python-object edges of encode_batch (csrc/pyfast.c); 
 
 __version__ = "0.3.3"
 __all__ = ["Tokenizer", "Trainer", "BpeTrainer", "WordPieceTrainer", "WordPieceModel", "UnigramTrainer", "UnigramModel", "WordLevelModel",
-           "CharBpeModel", "ByteLevelBpeModel", "Normalizer", "PreTokenizer", "Decoder", "PostProcessor", "Encoding",
-           "BatchEncoding", "PanicException", "UnsupportedConfigError", "DeviceError", "__version__"]
+           "CharBpeModel", "ByteLevelBpeModel", "Normalizer", "PreTokenizer", "Decoder", "PostProcessor", "PipelineTokenizer",
+           "parse_tokenizer_json", "Encoding", "BatchEncoding", "PanicException", "UnsupportedConfigError", "DeviceError", "__version__"]
 
 
 class PanicException(BaseException):
@@ -163,6 +163,7 @@ from .normalizers import Normalizer  # noqa: E402
 from .pretokenizers import PreTokenizer  # noqa: E402
 from .decoders import Decoder  # noqa: E402
 from .postprocessors import PostProcessor  # noqa: E402
+from .pipeline import PipelineTokenizer, parse_tokenizer_json  # noqa: E402
 
 
 class Tokenizer:

@@ -238,6 +238,28 @@ class PpInfo(ctypes.Structure):  # ctok_postprocessor_info
                                                "width")]
 
 
+class PipelineTables(ctypes.Structure):  # include/ctok_pipeline.h ctok_pipeline_tables
+    _fields_ = [("vocab_bytes", ctypes.c_void_p), ("vocab_off", ctypes.c_void_p), ("vocab_id", ctypes.c_void_p), ("n_vocab", ctypes.c_uint64),
+                ("merge_bytes", ctypes.c_void_p), ("merge_off", ctypes.c_void_p), ("n_merge_strings", ctypes.c_uint64),
+                ("added_bytes", ctypes.c_void_p), ("added_off", ctypes.c_void_p), ("added_id", ctypes.c_void_p),
+                ("added_flags", ctypes.c_void_p), ("n_added", ctypes.c_uint64)]
+
+
+class PipelineLimits(ctypes.Structure):  # ctok_pipeline_limits_t
+    _fields_ = [("tier1", ctypes.c_uint32), ("tier2", ctypes.c_uint32), ("max_word_symbols", ctypes.c_uint64),
+                ("max_flagged_word_bytes", ctypes.c_uint64), ("max_added_tokens", ctypes.c_uint64),
+                ("max_added_token_bytes", ctypes.c_uint64), ("max_merges", ctypes.c_uint64), ("max_added_group_bytes", ctypes.c_uint64),
+                ("max_batch_bytes", ctypes.c_uint64)]
+
+
+class PipelineInfo(ctypes.Structure):  # ctok_pipeline_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("texts", "bytes_in", "bytes_normalized", "bytes_words", "words", "segments", "symbols",
+                                               "ids", "tier2_segments", "tier3_segments", "max_segment_symbols")]
+
+
+CTOK_PIPELINE_TOKENIZE = 1
+CTOK_PIPELINE_STAGES = 6
+
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -406,6 +428,15 @@ SIGS = {
     "ctok_postprocessor_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), _u64, _u64p]),
     "ctok_postprocessor_stage_name": (ctypes.c_char_p, [_p, _u64]),
     "ctok_postprocessor_stats": (ctypes.c_int, [_p, ctypes.POINTER(PpInfo)]),
+    # include/ctok_pipeline.h
+    "ctok_pipeline_create": (ctypes.c_int, [ctypes.POINTER(PipelineTables), _p, _p, ctypes.c_int, ctypes.POINTER(_p)]),
+    "ctok_pipeline_destroy": (None, [_p]),
+    "ctok_pipeline_encode_batch": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.c_uint32, ctypes.POINTER(_p), ctypes.POINTER(_p)]),
+    "ctok_pipeline_encode_batch_device": (ctypes.c_int, [_p, _p, _p, _u64, _u64, ctypes.c_uint32, _p, _u64, _p, _u64p, _p]),
+    "ctok_pipeline_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double)]),
+    "ctok_pipeline_stage_name": (ctypes.c_char_p, [_u64]),
+    "ctok_pipeline_limits": (None, [_p, ctypes.POINTER(PipelineLimits)]),
+    "ctok_pipeline_stats": (ctypes.c_int, [_p, ctypes.POINTER(PipelineInfo)]),
 }
 
 for _name, (_res, _args) in SIGS.items():

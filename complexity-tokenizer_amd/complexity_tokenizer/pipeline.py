@@ -1,0 +1,517 @@
+"""`PipelineTokenizer`: a BPE tokenizer.json with any normaliser, pre-tokenizer, decoder and
+post-processor -- the reference's HuggingFaceTokenizer (src/huggingface/mod.rs:247-334, :551-613,
+:711-769, :1080-1101 over src/huggingface/parsing.rs:10-364 and src/bpe.rs:52-153) -- on the GPU, through
+include/ctok_pipeline.h.
+
+`Tokenizer` runs the fused ByteLevel path and refuses every other file; this class chains the
+stand-alone stages on the device instead: Normalizer -> PreTokenizer -> the id-keyed word BPE with the
+added-token loop inside every word (csrc/wordbpe.hip), without a trip through host memory.  Decode
+goes through the loaded Decoder (`Decoder.fuse()` when the file names none) over the vocabulary's
+strings.  The quirks are the reference's: a char without a one-char vocab string is dropped, a pair's
+new id is the filtered merge list's entry at the pair's unfiltered rank, and a pair whose rank is past
+that list raises PanicException as soon as it stands adjacent in a word.  There is no CPU fallback.
+Refusals the reference does not have are listed in include/ctok_pipeline.h.
+"""
+from __future__ import annotations
+
+import ctypes
+import json
+
+import numpy as np
+
+from . import _native as _n
+from . import _raise, _split_lists, pack_ids, pack_texts
+from .decoders import Decoder
+from .models import _WHITE_SPACE
+from .normalizers import Normalizer
+from .postprocessors import PostProcessor
+from .pretokenizers import PreTokenizer
+
+# ---- src/huggingface/parsing.rs as a pure function -------------------------------------------------------
+
+
+def _named(value):
+    """A component that names its type: (object, type); else None, the default arm of parsing.rs."""
+    if not isinstance(value, dict) or "type" not in value:
+        return None
+    return value, value["type"] if isinstance(value["type"], str) else ""
+
+
+def _get(obj, key, kind, default):
+    v = obj.get(key)
+    if kind is int:
+        return v if type(v) is int and 0 <= v < 1 << 64 else default  # serde_json as_u64
+    return v if isinstance(v, kind) else default
+
+
+def _first_char(obj, key, default):
+    v = obj.get(key)
+    return v[0] if isinstance(v, str) and len(v) > 0 else default
+
+
+def _members(obj, key, parse):
+    """A Sequence: members that parse to none are skipped; no array, or nothing left, is none."""
+    v = obj.get(key)
+    if not isinstance(v, list):
+        return None
+    kept = []
+    for m in v:
+        p = parse(m)
+        if p is not None:
+            kept.append(p)
+    return ("sequence", kept) if kept else None
+
+
+def _parse_normalizer(value):
+    named = _named(value)
+    if named is None:
+        return ("nfc",)
+    obj, t = named
+    simple = {"NFC": "nfc", "NFD": "nfd", "NFKC": "nfkc", "NFKD": "nfkd", "Lowercase": "lowercase", "Strip": "strip",
+              "StripAccents": "strip_accents"}
+    if t in simple:
+        return (simple[t],)
+    if t == "Replace":
+        pattern = obj.get("pattern")
+        return ("replace", _get(pattern, "String", str, "") if isinstance(pattern, dict) else "", _get(obj, "content", str, ""))
+    if t == "Prepend":
+        return ("prepend", _get(obj, "prepend", str, ""))
+    if t == "Sequence":
+        return _members(obj, "normalizers", _parse_normalizer)
+    if t == "BertNormalizer":
+        return ("bert", _get(obj, "clean_text", bool, True), _get(obj, "handle_chinese_chars", bool, True),
+                _get(obj, "strip_accents", bool, None), _get(obj, "lowercase", bool, True))
+    if t == "Precompiled":
+        # the reference keeps the charsmap string as one (s, s) entry: a replace of s by itself
+        s = obj.get("precompiled_charsmap")
+        return ("precompiled", [(s, s)] if isinstance(s, str) else [])
+    return None
+
+
+def _parse_pre_tokenizer(value):
+    named = _named(value)
+    if named is None:
+        return ("byte_level", False)
+    obj, t = named
+    simple = {"Whitespace": "whitespace", "WhitespaceSplit": "whitespace_split", "Punctuation": "punctuation",
+              "BertPreTokenizer": "bert", "UnicodeScripts": "unicode_scripts"}
+    if t in simple:
+        return (simple[t],)
+    if t == "ByteLevel":
+        return ("byte_level", _get(obj, "add_prefix_space", bool, False))
+    if t == "Metaspace":
+        return ("metaspace", _first_char(obj, "replacement", "▁"), _get(obj, "add_prefix_space", bool, True))
+    if t == "CharDelimiterSplit":
+        return ("char_delimiter_split", _first_char(obj, "delimiter", " "))
+    if t == "Digits":
+        return ("digits", _get(obj, "individual_digits", bool, False))
+    if t == "Split":
+        pattern = obj.get("pattern")
+        behavior = _get(obj, "behavior", str, "Removed")
+        if behavior not in ("Isolated", "MergedWithPrevious", "MergedWithNext", "Contiguous"):
+            behavior = "Removed"
+        return ("split", _get(pattern, "Regex", str, "") if isinstance(pattern, dict) else "", behavior, _get(obj, "invert", bool, False))
+    if t == "Sequence":
+        return _members(obj, "pretokenizers", _parse_pre_tokenizer)
+    return None
+
+
+def _parse_decoder(value):
+    named = _named(value)
+    if named is None:
+        return ("byte_level",)
+    obj, t = named
+    if t == "ByteLevel":
+        return ("byte_level",)
+    if t == "Metaspace":
+        return ("metaspace", _first_char(obj, "replacement", "▁"), _get(obj, "add_prefix_space", bool, True))
+    if t == "WordPiece":
+        return ("wordpiece", _get(obj, "prefix", str, "##"), _get(obj, "cleanup", bool, True))
+    if t == "BPE":
+        return ("bpe", _get(obj, "suffix", str, "</w>"))
+    if t == "CTC":
+        return ("ctc", _get(obj, "pad_token", str, "<pad>"), _get(obj, "word_delimiter_token", str, None))
+    if t == "Fuse":
+        return ("fuse",)
+    if t == "Strip":
+        return ("strip", _first_char(obj, "content", " "), _get(obj, "start", int, 0), _get(obj, "stop", int, 0))
+    if t == "Sequence":
+        return _members(obj, "decoders", _parse_decoder)
+    return None
+
+
+def _template_string(items):
+    parts = []
+    for item in items:
+        if not isinstance(item, dict):
+            continue
+        if "SpecialToken" in item:
+            inner = item["SpecialToken"]
+            tid = inner.get("id") if isinstance(inner, dict) else None
+            if isinstance(tid, str):
+                parts.append(tid)
+        elif "Sequence" in item:
+            inner = item["Sequence"]
+            sid = inner.get("id") if isinstance(inner, dict) else None
+            if isinstance(sid, str):
+                parts.append("$" + sid)
+    return " ".join(parts)
+
+
+def _parse_post_processor(value, special):
+    named = _named(value)
+    if named is None:
+        return None
+    obj, t = named
+    if t == "TemplateProcessing":
+        single, pair = obj.get("single"), obj.get("pair")
+        return ("template", _template_string(single) if isinstance(single, list) else "<s> $A </s>",
+                _template_string(pair) if isinstance(pair, list) else None, [(k, v) for k, v in special.items()])
+    if t == "RobertaProcessing":
+        return ("roberta", ("<s>", special.get("<s>", 0)), ("</s>", special.get("</s>", 2)), False)
+    if t == "BertProcessing":
+        return ("bert", ("[CLS]", special.get("[CLS]", 101)), ("[SEP]", special.get("[SEP]", 102)))
+    return None
+
+
+def _parse_merges(items):
+    """deserialize_merges (mod.rs:56-101): strings as they are, arrays of two strings joined by ' ',
+    anything else skipped; then only what splits into exactly two parts at ' ' (mod.rs:252-264)."""
+    if not isinstance(items, list):
+        raise IOError("invalid type for `merges`: a sequence of strings or arrays of two strings expected")
+    out = []
+    for item in items:
+        if isinstance(item, list):
+            if len(item) != 2 or not isinstance(item[0], str) or not isinstance(item[1], str):
+                continue
+            item = item[0] + " " + item[1]
+        elif not isinstance(item, str):
+            continue
+        parts = item.split(" ")
+        if len(parts) == 2:
+            out.append((parts[0], parts[1]))
+    return out
+
+
+def parse_tokenizer_json(obj) -> dict:
+    """The rules of from_tokenizer_json_with_config and parsing.rs over a parsed tokenizer.json, with no
+    device: a spec of constructor calls.  `vocab` {str: id}, `merges` [(left, right)], `added_tokens`
+    [dict], and the four components as nested tuples named after the constructors of Normalizer,
+    PreTokenizer, Decoder and PostProcessor -- ("nfkc",), ("metaspace", "▁", True), ("sequence", [...])
+    -- or None where the reference has none."""
+    if not isinstance(obj, dict) or not isinstance(obj.get("model"), dict):
+        raise IOError("missing field `model`")
+    model = obj["model"]
+    vocab = model.get("vocab")
+    if not isinstance(vocab, dict):
+        raise IOError("missing field `vocab`")
+    for k, v in vocab.items():
+        if type(v) is not int or not 0 <= v < 1 << 32:
+            raise IOError("invalid value for vocab entry %r, expected u32" % (k,))
+    added = []
+    for t in obj.get("added_tokens") or []:
+        if not isinstance(t, dict) or type(t.get("id")) is not int or not isinstance(t.get("content"), str) \
+                or not isinstance(t.get("special"), bool):
+            raise IOError("invalid added token: `id` (u32), `content` (string) and `special` (boolean) are required")
+        added.append(dict(id=t["id"], content=t["content"], special=t["special"], single_word=_get(t, "single_word", bool, False),
+                          lstrip=_get(t, "lstrip", bool, False), rstrip=_get(t, "rstrip", bool, False),
+                          normalized=_get(t, "normalized", bool, False)))
+    special = {}
+    for t in added:
+        if t["special"]:
+            special[t["content"]] = t["id"]
+    return {"vocab": dict(vocab), "merges": _parse_merges(model.get("merges", [])), "added_tokens": added,
+            "normalizer": _parse_normalizer(obj.get("normalizer")), "pre_tokenizer": _parse_pre_tokenizer(obj.get("pre_tokenizer")),
+            "decoder": _parse_decoder(obj.get("decoder")), "post_processor": _parse_post_processor(obj.get("post_processor"), special)}
+
+
+def _build(cls, spec, device):
+    """The component object of a spec tuple (None stays None)."""
+    if spec is None:
+        return None
+    kind = spec[0]
+    if kind == "sequence":
+        return cls.sequence([_build(cls, s, device) for s in spec[1]], device=device)
+    if cls is PostProcessor:
+        if kind == "template":
+            return PostProcessor.template(spec[1], spec[2], list(spec[3]), device=device)
+        if kind == "bert":
+            return PostProcessor.bert(spec[1][0], spec[1][1], spec[2][0], spec[2][1], device=device)
+        return PostProcessor.roberta(spec[1][0], spec[1][1], spec[2][0], spec[2][1], spec[3], device=device)
+    return getattr(cls, kind)(*spec[1:], device=device)
+
+
+_CLEANUP = ((" .", "."), (" ,", ","), (" !", "!"), (" ?", "?"), (" :", ":"), (" ;", ";"), ('" ', '"'), (' "', '"'), ("' ", "'"),
+            (" '", "'"), ("( ", "("), (" )", ")"), ("[ ", "["), (" ]", "]"), (" - ", "-"))
+_WS_TABLE = {ord(c): " " for c in _WHITE_SPACE}
+
+
+def _clean_up(text: str) -> str:
+    """clean_up_tokenization_spaces (mod.rs:749-769): fifteen replaces, then split_whitespace with
+    Rust's white-space set, joined by ' '.  Host string work."""
+    for a, b in _CLEANUP:
+        text = text.replace(a, b)
+    return " ".join(w for w in text.translate(_WS_TABLE).split(" ") if w)
+
+
+class PipelineTokenizer:
+    """A BPE tokenizer with any normaliser and pre-tokenizer whose encode runs on an MI355X."""
+
+    def __init__(self, vocab, merges, normalizer, pre_tokenizer, decoder, post_processor, added_tokens, device):
+        self._vocab = dict(vocab)
+        self._id_to_token = {v: k for k, v in self._vocab.items()}
+        self._normalizer, self._pre_tokenizer, self._decoder, self._post_processor = normalizer, pre_tokenizer, decoder, post_processor
+        self._added = [dict(t) for t in added_tokens]
+        self._special = {t["content"]: t["id"] for t in self._added if t.get("special", False)}
+        self._special_ids = None
+        self._decode_with = None
+        self.device = device
+        self.last_stats = None
+        keys = [k.encode("utf-8") for k in self._vocab]
+        ms = [s.encode("utf-8") for ab in merges for s in ab]
+        ab = [t["content"].encode("utf-8") for t in self._added]
+
+        def packed(items):
+            off = np.zeros(len(items) + 1, dtype=np.uint64)
+            if items:
+                np.cumsum([len(x) for x in items], out=off[1:])
+            return np.frombuffer(b"".join(items) + b"\0" * 16, dtype=np.uint8), off
+
+        vb, voff = packed(keys)
+        mb, moff = packed(ms)
+        abb, aoff = packed(ab)
+        vid = np.asarray(list(self._vocab.values()) + [0], dtype=np.uint32)
+        aid = np.asarray([int(t["id"]) for t in self._added] + [0], dtype=np.uint32)
+        bits = {"special": 1, "single_word": 2, "lstrip": 4, "rstrip": 8, "normalized": 16}
+        afl = np.asarray([sum(v for k, v in bits.items() if t.get(k, False)) for t in self._added] + [0], dtype=np.uint8)
+        tb = _n.PipelineTables(vb.ctypes.data, voff.ctypes.data, vid.ctypes.data, len(keys), mb.ctypes.data, moff.ctypes.data, len(ms),
+                               abb.ctypes.data, aoff.ctypes.data, aid.ctypes.data, afl.ctypes.data, len(ab))
+        h = ctypes.c_void_p()
+        rc = _n.lib.ctok_pipeline_create(ctypes.byref(tb), normalizer._h if normalizer is not None else None,
+                                         pre_tokenizer._h if pre_tokenizer is not None else None, device, ctypes.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        lib = getattr(_n, "lib", None) if _n is not None else None  # (None at interpreter teardown)
+        if h and lib is not None:
+            lib.ctok_pipeline_destroy(h)
+            self._h = None
+
+    def __repr__(self):
+        return "PipelineTokenizer(vocab_size=%d, normalizer=%r, pre_tokenizer=%r, device=%d)" % (
+            self.vocab_size, self._normalizer, self._pre_tokenizer, self.device)
+
+    # ------------------------------------------------------------------ constructors
+    @staticmethod
+    def from_components(vocab, merges, normalizer=None, pre_tokenizer=None, decoder=None, post_processor=None, added_tokens=(),
+                        device=None) -> "PipelineTokenizer":
+        """vocab {token: id}; merges [(left, right)] in rank order; the components are Normalizer,
+        PreTokenizer, Decoder and PostProcessor objects or None (no normaliser; the whole text is one
+        word; the vocab strings joined; no post-processor); added_tokens are dicts with the
+        tokenizer.json fields.  All components must be on one device (ValueError otherwise)."""
+        for name, c, cls in (("normalizer", normalizer, Normalizer), ("pre_tokenizer", pre_tokenizer, PreTokenizer),
+                             ("decoder", decoder, Decoder), ("post_processor", post_processor, PostProcessor)):
+            if c is not None and not isinstance(c, cls):
+                raise TypeError("argument '%s': '%s' object cannot be converted to '%s'" % (name, type(c).__name__, cls.__name__))
+        devs = {c.device for c in (normalizer, pre_tokenizer, decoder, post_processor) if c is not None}
+        if device is not None:
+            devs.add(int(device))
+        if len(devs) > 1:
+            raise ValueError("from_components: the components are on devices %s; all must be on one" % sorted(devs))
+        merges = [(a, b) for a, b in merges]
+        for a, b in merges:
+            if not isinstance(a, str) or not isinstance(b, str):
+                raise TypeError("argument 'merges': expected pairs of str")
+        added = []
+        for t in added_tokens:
+            if not isinstance(t, dict) or "id" not in t or not isinstance(t.get("content"), str):
+                raise TypeError("argument 'added_tokens': expected dicts with `id` and `content`")
+            added.append(t)
+        return PipelineTokenizer(vocab, merges, normalizer, pre_tokenizer, decoder, post_processor, added, devs.pop() if devs else 0)
+
+    @staticmethod
+    def from_spec(spec: dict, device: int = 0) -> "PipelineTokenizer":
+        """From what parse_tokenizer_json returns.  A `split` pattern PreTokenizer cannot run raises
+        UnsupportedConfigError, as it does there."""
+        return PipelineTokenizer.from_components(
+            spec["vocab"], spec["merges"], _build(Normalizer, spec["normalizer"], device), _build(PreTokenizer, spec["pre_tokenizer"], device),
+            _build(Decoder, spec["decoder"], device), _build(PostProcessor, spec["post_processor"], device), spec["added_tokens"], device)
+
+    @staticmethod
+    def from_str(json_text: str, device: int = 0) -> "PipelineTokenizer":
+        """HuggingFaceTokenizer::from_str (mod.rs:168-173)."""
+        try:
+            obj = json.loads(json_text)
+        except ValueError as e:
+            raise IOError(str(e)) from None
+        return PipelineTokenizer.from_spec(parse_tokenizer_json(obj), device)
+
+    @staticmethod
+    def from_file(path: str, device: int = 0) -> "PipelineTokenizer":
+        """HuggingFaceTokenizer::from_file (mod.rs:159-166)."""
+        with open(path, "r", encoding="utf-8") as f:
+            return PipelineTokenizer.from_str(f.read(), device)
+
+    # ------------------------------------------------------------------ getters
+    @property
+    def vocab_size(self) -> int:
+        return len(self._vocab)
+
+    def token_to_id(self, token: str):
+        return self._vocab.get(token)
+
+    def id_to_token(self, id: int):
+        return self._id_to_token.get(id)
+
+    @property
+    def special_tokens(self) -> dict:
+        return dict(self._special)
+
+    @property
+    def normalizer(self):
+        return self._normalizer
+
+    @property
+    def pre_tokenizer(self):
+        return self._pre_tokenizer
+
+    @property
+    def decoder(self):
+        return self._decoder
+
+    @property
+    def post_processor(self):
+        """The loaded PostProcessor or None: chain it with process_packed / process_padded over what
+        encode_batch_flat returns."""
+        return self._post_processor
+
+    @staticmethod
+    def limits(handle=None) -> dict:
+        lim = _n.PipelineLimits()
+        _n.lib.ctok_pipeline_limits(handle, ctypes.byref(lim))
+        return {k: int(getattr(lim, k)) for k, _ in lim._fields_}
+
+    # ------------------------------------------------------------------ encode
+    def _read_stats(self):
+        ms = (ctypes.c_double * _n.CTOK_PIPELINE_STAGES)()
+        info = _n.PipelineInfo()
+        _n.lib.ctok_pipeline_stage_ms(self._h, ms)
+        _n.lib.ctok_pipeline_stats(self._h, ctypes.byref(info))
+        st = {k: int(getattr(info, k)) for k, _ in info._fields_}
+        st["stages"] = [(_n.lib.ctok_pipeline_stage_name(i).decode(), ms[i]) for i in range(_n.CTOK_PIPELINE_STAGES)]
+        self.last_stats = st
+
+    def encode_packed(self, text, off, tokenize: bool = False):
+        """A packed batch (uint8 UTF-8 buffer, uint64 offsets[D + 1]) -> (ids uint32[T], tok_off uint64[D + 1])."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        if off.ndim != 1 or off.size < 1 or text.ndim != 1:
+            raise ValueError("encode_packed: text and off must be 1-D, off with n + 1 entries")
+        n = off.size - 1
+        if int(off[n]) > text.size:
+            raise ValueError("encode_packed: the offsets reach past the text")
+        ids_p, off_p = ctypes.c_void_p(), ctypes.c_void_p()
+        rc = _n.lib.ctok_pipeline_encode_batch(self._h, text.ctypes.data, off.ctypes.data, n, _n.CTOK_PIPELINE_TOKENIZE if tokenize else 0,
+                                               ctypes.byref(ids_p), ctypes.byref(off_p))
+        if rc:
+            _raise(rc)
+        self._read_stats()
+        tok_off = np.ctypeslib.as_array(ctypes.cast(off_p, ctypes.POINTER(ctypes.c_uint64)), shape=(n + 1,)).copy()
+        total = int(tok_off[n])
+        ids = np.ctypeslib.as_array(ctypes.cast(ids_p, ctypes.POINTER(ctypes.c_uint32)), shape=(total,)).copy() if total \
+            else np.zeros(0, dtype=np.uint32)
+        return ids, tok_off
+
+    def encode_packed_device(self, d_text: int, d_off: int, n_docs: int, n_bytes: int, d_ids: int, ids_cap: int, d_tok_off: int,
+                             stream: int = 0, tokenize: bool = False) -> int:
+        """The same over raw device pointers (ints; e.g. torch tensors' data_ptr()) of this tokenizer's
+        device, ordered on the HIP stream `stream` (0: the default stream).  d_ids has room for ids_cap
+        uint32, d_tok_off for n_docs + 1 uint64.  Returns the number of ids; raises BufferError carrying
+        `.needed` when ids_cap is too small, with nothing written.  The bytes are taken as they are.
+        Returns after the work is done."""
+        need = ctypes.c_uint64()
+        rc = _n.lib.ctok_pipeline_encode_batch_device(self._h, d_text, d_off, n_docs, n_bytes, _n.CTOK_PIPELINE_TOKENIZE if tokenize else 0,
+                                                      d_ids, ids_cap, d_tok_off, ctypes.byref(need), stream)
+        if rc == _n.CTOK_E_CAPACITY and need.value > ids_cap:
+            e = BufferError("encode_packed_device: the ids need %d entries, ids_cap is %d" % (need.value, ids_cap))
+            e.needed = int(need.value)
+            raise e
+        if rc:
+            _raise(rc)
+        self._read_stats()
+        return int(need.value)
+
+    def encode_batch_flat(self, texts):
+        """list[str] -> (ids uint32[T], tok_off uint64[D + 1])"""
+        text, off = pack_texts(texts)
+        return self.encode_packed(text, off)
+
+    def encode_batch(self, texts) -> list:
+        """mod.rs:694-696"""
+        return _split_lists(*self.encode_batch_flat(texts))
+
+    def encode(self, text: str) -> list:
+        """mod.rs:551-613"""
+        if not isinstance(text, str):
+            raise TypeError("'%s' object cannot be converted to 'PyString'" % type(text).__name__)
+        return self.encode_batch([text])[0]
+
+    def tokenize_batch(self, texts) -> list:
+        text, off = pack_texts(texts)
+        ids, tok_off = self.encode_packed(text, off, tokenize=True)
+        names = self._id_to_token
+        ids, o = ids.tolist(), tok_off.tolist()
+        return [[names[i] for i in ids[o[d]:o[d + 1]] if i in names] for d in range(len(o) - 1)]
+
+    def tokenize(self, text: str) -> list:
+        """mod.rs:1080-1101: the word BPE without the added-token loop, as vocab strings; an id
+        without a vocab string is dropped."""
+        if not isinstance(text, str):
+            raise TypeError("'%s' object cannot be converted to 'PyString'" % type(text).__name__)
+        return self.tokenize_batch([text])[0]
+
+    # ------------------------------------------------------------------ decode
+    def _decoder_with_vocab(self):
+        if self._decode_with is None:
+            dec = self._decoder
+            if dec is None:
+                dec = Decoder.fuse(device=self.device)  # BpeTokenizer::decode: the vocab strings joined
+            elif dec._has_vocab:
+                dec = Decoder(dec._steps, dec.device, repr(dec))  # (the caller's decoder keeps its own vocabulary)
+            dec.set_vocab(self._id_to_token)
+            self._decode_with = dec
+        return self._decode_with
+
+    def decode_batch_with_options(self, batch, skip_special_tokens: bool = False, clean_up_tokenization_spaces: bool = True) -> list:
+        """decode_impl (mod.rs:711-747) of every id list: optionally without the ids whose vocab string
+        is a special token, ids without a vocab string dropped, the decoder on the device, then
+        optionally the clean-up."""
+        ids, off = pack_ids(batch)
+        if skip_special_tokens and self._special:
+            if self._special_ids is None:
+                self._special_ids = np.asarray(sorted(i for i, t in self._id_to_token.items() if t in self._special), dtype=np.uint32)
+            keep = ~np.isin(ids, self._special_ids)
+            kept_before = np.concatenate(([0], np.cumsum(keep, dtype=np.uint64)))
+            ids, off = ids[keep], kept_before[off.astype(np.int64)].astype(np.uint64)
+        dec = self._decoder_with_vocab()
+        text, text_off = dec.decode_ids_packed(ids, off)
+        raw, o = text.tobytes(), text_off.tolist()
+        out = [raw[o[i]:o[i + 1]].decode("utf-8") for i in range(len(o) - 1)]
+        return [_clean_up(t) for t in out] if clean_up_tokenization_spaces else out
+
+    def decode_batch(self, batch) -> list:
+        """mod.rs:771-773"""
+        return self.decode_batch_with_options(batch, False, True)
+
+    def decode_with_options(self, ids, skip_special_tokens: bool = False, clean_up_tokenization_spaces: bool = True) -> str:
+        """mod.rs:702-709"""
+        if isinstance(ids, (str, bytes)):
+            raise TypeError("Can't extract `str` to `Vec`")
+        return self.decode_batch_with_options([ids], skip_special_tokens, clean_up_tokenization_spaces)[0]
+
+    def decode(self, ids) -> str:
+        """mod.rs:698-700"""
+        return self.decode_with_options(ids, False, True)

@@ -1,0 +1,483 @@
+// Host runtime of the pipeline tokenizer behind include/ctok_pipeline.h: the reference's
+// HuggingFaceTokenizer (src/huggingface/mod.rs:247-334, :551-613, :1080-1101, Complexity-ML/
+// complexity-tokenizer v0.3.3) with any normaliser and pre-tokenizer.  wordbpe_compile.cpp turns
+// vocab, merges and added tokens into tables at create; a call chains, on one stream and without a
+// trip through host memory,
+//   ctok_normalizer_run_device -> ctok_pretokenizer_run_device -> the id-keyed word BPE (wordbpe.hip):
+//   segments -> symbols -> merges -> emit
+// The buffers only grow.  A component that reports CTOK_E_CAPACITY gets the size it asked for and
+// runs once more.  Every count is read back before the stage that is sized by it runs, so a segment
+// above the cap, a flagged word above the work bound and a batch that reaches 4 GiB fail the call
+// before any merge kernel.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/ctok_pipeline.h"
+#include "ctok_internal.h"  // ctok_dev::scan_u32, scan_tmp_elems
+#include "gen/alnum_data.h"
+#include "host_common.h"
+#include "knobs.h"
+#include "train_host_common.h"
+#include "wordbpe_compile.h"
+#include "wordbpe_internal.h"
+
+using namespace ctok_wb;
+using ctok_host::throw_error;
+using ctok_train_host::DBuf;
+
+static_assert(wordbpe::kErrUnsupported == CTOK_E_UNSUPPORTED && wordbpe::kErrArg == CTOK_E_ARG &&
+                  wordbpe::kErrCapacity == CTOK_E_CAPACITY,
+              "wordbpe_compile.h repeats the codes of ctok.h");
+
+namespace {
+
+constexpr uint64_t kRefuseFrom = 0xFFFFFF00ull;  // bytes, words or texts of one call: 4 GiB less the slack of the u32 scans
+
+const char* const kStageNames[CTOK_PIPELINE_STAGES] = {"normalize", "pre_tokenize", "segments", "symbols", "merges", "emit"};
+
+uint64_t word_cap() {
+  uint64_t cap = kMaxWordSymbols;
+  if (auto e = ctok_rt::env_u64("CTOK_PIPELINE_MAX_WORD_SYMBOLS")) cap = std::min<uint64_t>(cap, *e);
+  return cap;
+}
+
+template <typename T>
+void upload(DBuf<T>& d, const T* src, size_t n, hipStream_t s) {
+  d.ensure(n + 1);
+  if (n) HIPT(hipMemcpyAsync(d.p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
+}
+
+// a component's error, with its message, as this call's
+[[noreturn]] void rethrow(int rc) { throw_error(rc, std::string(ctok_last_error())); }
+
+bool valid_utf8(const uint8_t* t, uint64_t a, uint64_t e) {
+  while (a < e) {
+    uint32_t cp = 0;
+    const uint32_t l = wordbpe::dec_char(t, a, e, &cp);
+    if (!l) return false;
+    a += l;
+  }
+  return true;
+}
+
+}  // namespace
+
+struct ctok_pipeline {
+  wordbpe::Compiled c;
+  ctok_normalizer* nz = nullptr;
+  ctok_pretokenizer* pt = nullptr;
+  int device = 0;
+  uint64_t cap = kMaxWordSymbols;
+  uint64_t flag_cap = kMaxFlaggedWordBytes;  // of this handle's added tokens (wordbpe_internal.h)
+  uint64_t match_cap = ~0ull;                // bytes of a batch the filter pass takes
+  hipStream_t own = nullptr;
+  hipEvent_t ev[CTOK_PIPELINE_STAGES + 1] = {};
+  double stage_ms[CTOK_PIPELINE_STAGES] = {};
+  ctok_pipeline_info info{};
+  // the tables
+  DBuf<wordbpe::CpSlot> d_cps;
+  DBuf<strmerge::PairSlot> d_pairs;
+  DBuf<uint8_t> d_abytes;
+  DBuf<uint32_t> d_aoff, d_aid, d_aflags, d_agroup, d_alo, d_ahi;
+  Tables T{};
+  // a call's buffers
+  DBuf<uint8_t> in_text, norm, words;
+  DBuf<uint64_t> in_off, norm_off, word_off, text_word, tok_off, state3;
+  DBuf<uint32_t> wbits, mbits, kbits, kpc, krank, wseg, segoff, nsym, soff, fcnt, wpos, sym, list2, list3, state, ctr, tmp, ids;
+  DBuf<wordbpe::Seg> segs;
+  Batch B{};
+  uint64_t n_ids = 0;
+  std::vector<uint32_t> h_ids;
+  std::vector<uint64_t> h_tok_off;
+
+  ~ctok_pipeline() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (own) (void)hipStreamDestroy(own);
+  }
+
+  void to_device() {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
+      (void)hipGetLastError();
+      throw_error(CTOK_E_DEVICE, "pipeline: no HIP device " + std::to_string(device));
+    }
+    HIPT(hipSetDevice(device));
+    HIPT(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
+    for (auto& e : ev) HIPT(hipEventCreate(&e));
+    upload(d_cps, c.cps.data(), c.cps.size(), own);
+    upload(d_pairs, c.pairs.data(), c.pairs.size(), own);
+    upload(d_abytes, c.a_bytes.data(), c.a_bytes.size(), own);
+    upload(d_aoff, c.a_off.data(), c.a_off.size(), own);
+    upload(d_aid, c.a_id.data(), c.a_id.size(), own);
+    upload(d_aflags, c.a_flags.data(), c.a_flags.size(), own);
+    upload(d_agroup, c.a_group.data(), c.a_group.size(), own);
+    upload(d_alo, wb_alnum_lo, (size_t)WB_N_ALNUM, own);
+    upload(d_ahi, wb_alnum_hi, (size_t)WB_N_ALNUM, own);
+    HIPT(hipStreamSynchronize(own));
+    T.pairs = wordbpe::PairView{d_pairs.p, (uint32_t)c.pairs.size() - 1};
+    T.cps = wordbpe::CpView{d_cps.p, (uint32_t)c.cps.size() - 1};
+    T.added = wordbpe::AddedView{d_abytes.p, d_aoff.p, d_aid.p, d_aflags.p, d_agroup.p, d_alo.p, d_ahi.p, (uint32_t)WB_N_ALNUM,
+                                 (uint32_t)c.a_id.size()};
+    for (int i = 0; i < 8; i++) T.first_byte[i] = c.first_byte[i];
+    if (c.max_group_bytes) {
+      flag_cap = std::min<uint64_t>(kMaxFlaggedWordBytes, kFlaggedWork / c.max_group_bytes);
+      match_cap = kMatchWork / c.max_group_bytes;
+    }
+  }
+
+  void scan(const uint32_t* in, uint32_t* out, uint64_t n, hipStream_t s) {  // out[n] = the total
+    tmp.ensure(ctok_dev::scan_tmp_elems(n + 1) + 64);
+    if (n) HIPT(ctok_dev::scan_u32(in, out, n, nullptr, tmp.p, tmp.cap, s));
+    else HIPT(hipMemsetAsync(out, 0, 4, s));
+  }
+
+  uint32_t read_u32(const uint32_t* d, hipStream_t s) {
+    uint32_t v = 0;
+    HIPT(hipMemcpyAsync(&v, d, 4, hipMemcpyDeviceToHost, s));
+    HIPT(hipStreamSynchronize(s));
+    return v;
+  }
+
+  // Everything up to the count of the ids (n_ids); emit() writes them.  n > 0.
+  void run(const uint8_t* d_text, const uint64_t* d_off, uint64_t n, uint64_t nb, uint32_t flags, hipStream_t s) {
+    HIPT(hipSetDevice(device));
+    for (double& t : stage_ms) t = 0;
+    info = ctok_pipeline_info{};
+    info.texts = n;
+    info.bytes_in = nb;
+    if (nb >= kRefuseFrom || n >= kRefuseFrom) throw_error(CTOK_E_CAPACITY, "pipeline: the input reaches 4 GiB");
+
+    // 1. the normaliser
+    HIPT(hipEventRecord(ev[0], s));
+    const uint8_t* text = d_text;
+    const uint64_t* off = d_off;
+    uint64_t tb = nb;
+    if (nz) {
+      norm.ensure(nb + 64);
+      norm_off.ensure(n + 1);
+      uint64_t need = 0;
+      int rc = ctok_normalizer_run_device(nz, d_text, d_off, n, nb, norm.p, norm.cap, norm_off.p, &need, s);
+      if (rc == CTOK_E_CAPACITY && need > norm.cap && need < kRefuseFrom) {
+        norm.ensure(need + 64);
+        rc = ctok_normalizer_run_device(nz, d_text, d_off, n, nb, norm.p, norm.cap, norm_off.p, &need, s);
+      }
+      if (rc) rethrow(rc);
+      text = norm.p;
+      off = norm_off.p;
+      tb = need;
+    }
+    info.bytes_normalized = tb;
+    HIPT(hipEventRecord(ev[1], s));
+
+    // 2. the pre-tokenizer; without one the whole normalised text is one word
+    const uint8_t* wtext = text;
+    const uint64_t* woff = off;
+    uint64_t wbytes = tb, n_words = n;
+    text_word.ensure(n + 1);
+    if (pt) {
+      words.ensure(tb + 64);
+      word_off.ensure(tb / 2 + n + 65);
+      uint64_t need_b = 0, need_w = 0;
+      int rc = ctok_pretokenizer_run_device(pt, text, off, n, tb, words.p, words.cap, word_off.p, word_off.cap - 1, text_word.p,
+                                            &need_b, &need_w, s);
+      if (rc == CTOK_E_CAPACITY && (need_b > words.cap || need_w > word_off.cap - 1) && need_b < kRefuseFrom && need_w < kRefuseFrom) {
+        words.ensure(need_b + 64);
+        word_off.ensure(need_w + 65);
+        rc = ctok_pretokenizer_run_device(pt, text, off, n, tb, words.p, words.cap, word_off.p, word_off.cap - 1, text_word.p,
+                                          &need_b, &need_w, s);
+      }
+      if (rc) rethrow(rc);
+      wtext = words.p;
+      woff = word_off.p;
+      wbytes = need_b;
+      n_words = need_w;
+    } else {
+      HIPT(launch_iota(text_word.p, n + 1, s));
+    }
+    if (wbytes + n_words >= kRefuseFrom) throw_error(CTOK_E_CAPACITY, "pipeline: the words reach 4 GiB");
+    info.bytes_words = wbytes;
+    info.words = n_words;
+    HIPT(hipEventRecord(ev[2], s));
+
+    // 3. the segments
+    const uint32_t n_w = (uint32_t)((wbytes + 31) / 32);
+    const bool with_added = !c.a_id.empty() && !(flags & CTOK_PIPELINE_TOKENIZE);
+    wbits.ensure((size_t)n_w + 1);
+    ctr.ensure(kNumCtr);
+    HIPT(hipMemsetAsync(wbits.p, 0, ((size_t)n_w + 1) * 4, s));
+    HIPT(hipMemsetAsync(ctr.p, 0, kNumCtr * 4, s));
+    HIPT(hipMemsetAsync(ctr.p + kCtrPanic, 0xFF, 4, s));
+    B = Batch{};
+    B.text = wtext;
+    B.n_bytes = (uint32_t)wbytes;
+    B.n_w = n_w;
+    B.word_off = woff;
+    B.n_words = (uint32_t)n_words;
+    B.text_word = text_word.p;
+    B.n_texts = n;
+    B.wbits = wbits.p;
+    B.ctr = ctr.p;
+    B.flag_cap = (uint32_t)flag_cap;
+    if (with_added && wbytes > match_cap)
+      throw_error(CTOK_E_UNSUPPORTED, "a batch of " + std::to_string(wbytes) + " bytes of words: the added tokens that share a "
+                                          "first byte hold " + std::to_string(c.max_group_bytes) + " bytes, and with them batches of more than " +
+                                          std::to_string(match_cap) + " bytes are not supported");
+    HIPT(launch_word_bits(B, s));
+    uint32_t n_segs = (uint32_t)n_words;
+    if (with_added) {
+      mbits.ensure((size_t)n_w + 1);
+      wseg.ensure(n_words + 1);
+      segoff.ensure(n_words + 1);
+      B.mbits = mbits.p;
+      B.wseg = wseg.p;
+      HIPT(launch_match_bits(T, B, s));
+      HIPT(launch_seg_count(T, B, s));
+      scan(wseg.p, segoff.p, n_words, s);
+      B.segoff = segoff.p;
+      uint32_t h_ctr[kNumCtr] = {};
+      HIPT(hipMemcpyAsync(h_ctr, ctr.p, kNumCtr * 4, hipMemcpyDeviceToHost, s));
+      n_segs = read_u32(segoff.p + n_words, s);
+      if (h_ctr[kCtrMaxFlagged])
+        throw_error(CTOK_E_UNSUPPORTED, "a word of " + std::to_string(h_ctr[kCtrMaxFlagged]) +
+                                            " bytes holds an added token: one thread walks such a word, words of more than " +
+                                            std::to_string(flag_cap) + " bytes are not supported with these added tokens");
+      if (n_segs > wbytes + n_words) throw_error(CTOK_E_DEVICE, "pipeline: more segments than bytes");
+    }
+    segs.ensure((size_t)n_segs + 1);
+    B.segs = segs.p;
+    B.n_segs = n_segs;
+    HIPT(launch_seg_write(T, B, s));
+    info.segments = n_segs;
+    HIPT(hipEventRecord(ev[3], s));
+
+    // 4. the initial symbols, the segments' sizes and classes
+    kbits.ensure((size_t)n_w + 1);
+    kpc.ensure((size_t)n_w + 1);
+    krank.ensure((size_t)n_w + 2);
+    B.kbits = kbits.p;
+    B.kpc = kpc.p;
+    B.krank = krank.p;
+    HIPT(launch_keep_bits(T, B, s));
+    scan(kpc.p, krank.p, (uint64_t)n_w + 1, s);
+    const uint32_t n_sym = read_u32(krank.p + n_w + 1, s);
+    if (n_sym > wbytes) throw_error(CTOK_E_DEVICE, "pipeline: more symbols than bytes");
+    sym.ensure((size_t)n_sym + 1);
+    nsym.ensure((size_t)n_segs + 1);
+    soff.ensure((size_t)n_segs + 1);
+    fcnt.ensure((size_t)n_segs + 1);
+    wpos.ensure((size_t)n_segs + 1);
+    // a segment of more than kTier1 symbols has more than kTier1 bytes, one of more than kTier2 more than kTier2
+    const uint64_t cap2 = wbytes / kTier1 + 1, cap3 = wbytes / kTier2 + 1;
+    list2.ensure(cap2);
+    list3.ensure(cap3);
+    state3.ensure(cap3);
+    B.sym = sym.p;
+    B.nsym = nsym.p;
+    B.soff = soff.p;
+    B.fcnt = fcnt.p;
+    B.wpos = wpos.p;
+    B.list2 = list2.p;
+    B.list3 = list3.p;
+    B.state3 = state3.p;
+    HIPT(launch_symbols(T, B, s));
+    HIPT(launch_seg_info(B, s));
+    HIPT(hipEventRecord(ev[4], s));
+    uint32_t h_ctr[kNumCtr] = {};
+    HIPT(hipMemcpyAsync(h_ctr, ctr.p, kNumCtr * 4, hipMemcpyDeviceToHost, s));
+    HIPT(hipStreamSynchronize(s));
+    const uint32_t n2 = h_ctr[kCtrList2], n3 = h_ctr[kCtrList3];
+    const uint64_t n_state = (uint64_t)h_ctr[kCtrState] | (uint64_t)h_ctr[kCtrState + 1] << 32;
+    if (n2 > cap2 || n3 > cap3 || n_state > n_sym) throw_error(CTOK_E_DEVICE, "pipeline: the segment list is out of bounds");
+    info.symbols = n_sym;
+    info.tier2_segments = n2;
+    info.tier3_segments = n3;
+    info.max_segment_symbols = h_ctr[kCtrMaxSym];
+    if (h_ctr[kCtrMaxSym] > cap)
+      throw_error(CTOK_E_UNSUPPORTED, "a word of " + std::to_string(h_ctr[kCtrMaxSym]) + " symbols: the merge loop is quadratic "
+                                          "in a word's length, words of more than " + std::to_string(cap) +
+                                          " symbols are not supported");
+
+    // 5. the merges
+    state.ensure(4 * n_state + 1);
+    B.state = state.p;
+    HIPT(launch_merge(T, B, n2, n3, s));
+    scan(fcnt.p, wpos.p, n_segs, s);
+    HIPT(hipEventRecord(ev[5], s));
+    const uint32_t panic_seg = read_u32(ctr.p + kCtrPanic, s);
+    if (panic_seg != wordbpe::kNoPanic) {
+      if (panic_seg >= n_segs) throw_error(CTOK_E_DEVICE, "pipeline: the panic report is out of bounds");
+      const uint32_t at = read_u32(soff.p + panic_seg, s);
+      if (at >= n_sym) throw_error(CTOK_E_DEVICE, "pipeline: the panic report is out of bounds");
+      const uint32_t rank = read_u32(sym.p + at, s);
+      throw_error(CTOK_E_PANIC, "index out of bounds: the len is " + std::to_string(c.n_filtered) + " but the index is " +
+                                    std::to_string(rank));
+    }
+    n_ids = read_u32(wpos.p + n_segs, s);
+    if (n_ids > (uint64_t)n_sym + n_segs) throw_error(CTOK_E_DEVICE, "pipeline: more ids than symbols");
+    info.ids = n_ids;
+  }
+
+  void emit(uint32_t* d_ids, uint64_t* d_tok_off, hipStream_t s) {
+    HIPT(launch_emit(B, d_ids, d_tok_off, s));
+    HIPT(hipEventRecord(ev[6], s));
+    HIPT(hipStreamSynchronize(s));
+    for (int i = 0; i < CTOK_PIPELINE_STAGES; i++) {
+      float ms = 0;
+      HIPT(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      stage_ms[i] = ms;
+    }
+  }
+};
+
+namespace {
+
+std::vector<std::string> strings_of(const uint8_t* bytes, const uint64_t* off, uint64_t n, const char* what) {
+  std::vector<std::string> out;
+  if (n && (!off || (off[n] && !bytes))) throw_error(CTOK_E_ARG, std::string("null ") + what);
+  out.reserve(n);
+  for (uint64_t i = 0; i < n; i++) {
+    if (off[i] > off[i + 1]) throw_error(CTOK_E_ARG, "offsets must not decrease");
+    out.emplace_back((const char*)bytes + off[i], off[i + 1] - off[i]);
+  }
+  return out;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ctok_pipeline_create(const ctok_pipeline_tables* tb, ctok_normalizer* nz, ctok_pretokenizer* pt, int device,
+                         ctok_pipeline** out) {
+  if (!out) return ctok_host::run_guarded([] { throw_error(CTOK_E_ARG, "null argument"); });
+  *out = nullptr;
+  return ctok_host::run_guarded([&] {
+    if (!tb || (tb->n_vocab && !tb->vocab_id) || (tb->n_added && (!tb->added_id || !tb->added_flags)))
+      throw_error(CTOK_E_ARG, "null argument");
+    if (tb->n_merge_strings & 1) throw_error(CTOK_E_ARG, "the merges are pairs: an odd number of strings was given");
+    const std::vector<std::string> vs = strings_of(tb->vocab_bytes, tb->vocab_off, tb->n_vocab, "vocab");
+    const std::vector<std::string> ms = strings_of(tb->merge_bytes, tb->merge_off, tb->n_merge_strings, "merges");
+    const std::vector<std::string> as = strings_of(tb->added_bytes, tb->added_off, tb->n_added, "added tokens");
+    std::vector<std::pair<std::string, uint32_t>> vocab;
+    vocab.reserve(vs.size());
+    for (uint64_t i = 0; i < vs.size(); i++) vocab.emplace_back(vs[i], tb->vocab_id[i]);
+    std::vector<std::pair<std::string, std::string>> merges;
+    merges.reserve(ms.size() / 2);
+    for (size_t i = 0; i + 1 < ms.size(); i += 2) merges.emplace_back(ms[i], ms[i + 1]);
+    std::vector<wordbpe::AddedToken> added;
+    for (uint64_t i = 0; i < as.size(); i++) {
+      const uint32_t f = tb->added_flags[i];
+      added.push_back(wordbpe::AddedToken{as[i], tb->added_id[i],
+                                          ((f & CTOK_PIPELINE_AT_SINGLE_WORD) ? (uint32_t)wordbpe::kSingleWord : 0u) |
+                                              ((f & CTOK_PIPELINE_AT_LSTRIP) ? (uint32_t)wordbpe::kLstrip : 0u) |
+                                              ((f & CTOK_PIPELINE_AT_RSTRIP) ? (uint32_t)wordbpe::kRstrip : 0u)});
+    }
+    auto p = std::make_unique<ctok_pipeline>();
+    p->nz = nz;
+    p->pt = pt;
+    p->device = device;
+    p->cap = word_cap();
+    std::string err;
+    const int rc = wordbpe::compile(vocab, merges, added, &p->c, &err);
+    if (rc != wordbpe::kOk) throw_error(rc, err);
+    p->to_device();
+    *out = p.release();
+  });
+}
+
+void ctok_pipeline_destroy(ctok_pipeline* p) { delete p; }
+
+int ctok_pipeline_encode_batch(ctok_pipeline* p, const uint8_t* utf8, const uint64_t* off, uint64_t n, uint32_t flags,
+                               const uint32_t** ids, const uint64_t** tok_off) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !ids || !tok_off || (n && (!off || (off[n] && !utf8)))) throw_error(CTOK_E_ARG, "null argument");
+    p->h_ids.clear();
+    p->h_tok_off.assign(n + 1, 0);
+    *ids = p->h_ids.data();
+    *tok_off = p->h_tok_off.data();
+    for (double& t : p->stage_ms) t = 0;
+    if (!n) return;
+    if (off[0] != 0) throw_error(CTOK_E_ARG, "offsets[0] must be 0");
+    for (uint64_t i = 0; i < n; i++) {
+      if (off[i] > off[i + 1]) throw_error(CTOK_E_ARG, "offsets must not decrease");
+      if (!valid_utf8(utf8, off[i], off[i + 1])) throw_error(CTOK_E_ARG, "text " + std::to_string(i) + " is not UTF-8");
+    }
+    const uint64_t nb = off[n];
+    if (nb >= kRefuseFrom || n >= kRefuseFrom) throw_error(CTOK_E_CAPACITY, "pipeline: the input reaches 4 GiB");
+    HIPT(hipSetDevice(p->device));
+    hipStream_t s = p->own;
+    p->in_text.ensure(nb + 64);
+    p->in_off.ensure(n + 1);
+    p->tok_off.ensure(n + 1);
+    if (nb) HIPT(hipMemcpyAsync(p->in_text.p, utf8, nb, hipMemcpyHostToDevice, s));
+    HIPT(hipMemcpyAsync(p->in_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    p->run(p->in_text.p, p->in_off.p, n, nb, flags, s);
+    p->ids.ensure(p->n_ids + 1);
+    p->emit(p->ids.p, p->tok_off.p, s);
+    p->h_ids.resize(p->n_ids);
+    if (p->n_ids) HIPT(hipMemcpyAsync(p->h_ids.data(), p->ids.p, p->n_ids * 4, hipMemcpyDeviceToHost, s));
+    HIPT(hipMemcpyAsync(p->h_tok_off.data(), p->tok_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPT(hipStreamSynchronize(s));
+    *ids = p->h_ids.data();
+    *tok_off = p->h_tok_off.data();
+  });
+}
+
+int ctok_pipeline_encode_batch_device(ctok_pipeline* p, const uint8_t* d_utf8, const uint64_t* d_off, uint64_t n, uint64_t nb,
+                                      uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_tok_off, uint64_t* n_ids_out,
+                                      void* stream) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !d_tok_off || !n_ids_out || (n && !d_off) || (nb && !d_utf8)) throw_error(CTOK_E_ARG, "null argument");
+    *n_ids_out = 0;
+    HIPT(hipSetDevice(p->device));
+    hipStream_t s = (hipStream_t)stream;
+    for (double& t : p->stage_ms) t = 0;
+    if (!n) {
+      HIPT(hipMemsetAsync(d_tok_off, 0, 8, s));
+      HIPT(hipStreamSynchronize(s));
+      return;
+    }
+    p->run(d_utf8, d_off, n, nb, flags, s);
+    *n_ids_out = p->n_ids;
+    if (p->n_ids > ids_cap)
+      throw_error(CTOK_E_CAPACITY, "ctok_pipeline_encode_batch_device: the ids need " + std::to_string(p->n_ids) + " entries");
+    if (p->n_ids && !d_ids) throw_error(CTOK_E_ARG, "null argument");
+    p->emit(d_ids, d_tok_off, s);
+  });
+}
+
+int ctok_pipeline_stage_ms(const ctok_pipeline* p, double out[CTOK_PIPELINE_STAGES]) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !out) throw_error(CTOK_E_ARG, "null argument");
+    for (int i = 0; i < CTOK_PIPELINE_STAGES; i++) out[i] = p->stage_ms[i];
+  });
+}
+
+const char* ctok_pipeline_stage_name(uint64_t i) { return i < CTOK_PIPELINE_STAGES ? kStageNames[i] : ""; }
+
+void ctok_pipeline_limits(const ctok_pipeline* p, ctok_pipeline_limits_t* out) {
+  if (!out) return;
+  out->tier1 = kTier1;
+  out->tier2 = kTier2;
+  out->max_word_symbols = p ? p->cap : word_cap();
+  out->max_flagged_word_bytes = p ? p->flag_cap : kMaxFlaggedWordBytes;
+  out->max_added_group_bytes = wordbpe::kMaxGroupBytes;
+  out->max_batch_bytes = p && p->match_cap < kRefuseFrom ? p->match_cap : kRefuseFrom - 1;
+  out->max_added_tokens = wordbpe::kMaxAdded;
+  out->max_added_token_bytes = wordbpe::kMaxAddedBytes;
+  out->max_merges = wordbpe::kMaxMerges;
+}
+
+int ctok_pipeline_stats(const ctok_pipeline* p, ctok_pipeline_info* out) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !out) throw_error(CTOK_E_ARG, "null argument");
+    *out = p->info;
+  });
+}
+
+}  // extern "C"

@@ -1,0 +1,133 @@
+/* ctok_pipeline.h -- C ABI of the pipeline tokenizer on the GPU.
+ *
+ * The reference's HuggingFaceTokenizer (Complexity-ML/complexity-tokenizer v0.3.3,
+ * src/huggingface/mod.rs:247-334, :551-613, :1080-1101) with any normaliser and any pre-tokenizer:
+ * a batch goes through a ctok_normalizer, a ctok_pretokenizer and the id-keyed word BPE
+ * (src/bpe.rs:52-153: one id per char of a word, a char without a one-char vocab string dropped,
+ * then lowest rank, leftmost, one merge per step) with the added-token loop inside every word
+ * (mod.rs:566-675), without a trip through host memory.  The rank / new-id quirk of
+ * BpeTokenizer::new is kept: a pair's new id is that of the filtered merge list at the pair's
+ * unfiltered rank, and a pair whose rank is past that list fails the call with CTOK_E_PANIC and the
+ * reference's message as soon as it is seen adjacent, for the lowest-numbered text that has one.
+ *
+ * Refusals the reference does not have: a vocab id of 2^32 - 1, more than 2^24 merges, more than
+ * 1024 added tokens, one of more than 1024 bytes, or added tokens that share a first byte and hold
+ * more than 32 KiB together (CTOK_E_UNSUPPORTED at create); a word segment of more symbols than
+ * ctok_pipeline_limits reports (CTOK_E_UNSUPPORTED before any merge kernel runs); a batch or an
+ * intermediate that reaches 4 GiB (CTOK_E_CAPACITY).  With added tokens a byte position can cost a
+ * compare of every token that shares its first byte, G bytes for the largest such group, so the work
+ * is bounded through G: a word that holds an added token may have min(2^20, 2^23 / G) bytes -- one
+ * thread walks it -- and a call's words 2^40 / G bytes (CTOK_E_UNSUPPORTED before the pass that would do
+ * the work); ctok_pipeline_limits reports both for a handle.
+ *
+ * Errors: 0 or a negative CTOK_E_* code (ctok.h), ctok_last_error() holds the message.  There is no
+ * CPU path: without a HIP device create returns CTOK_E_DEVICE.  A handle keeps its grow-only device
+ * buffers and is used by one thread at a time.
+ */
+#ifndef CTOK_PIPELINE_H
+#define CTOK_PIPELINE_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "ctok.h"
+#include "ctok_normalizer.h"
+#include "ctok_pretokenizer.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct ctok_pipeline ctok_pipeline;
+
+/* added_flags bits */
+#define CTOK_PIPELINE_AT_SPECIAL 1u
+#define CTOK_PIPELINE_AT_SINGLE_WORD 2u
+#define CTOK_PIPELINE_AT_LSTRIP 4u
+#define CTOK_PIPELINE_AT_RSTRIP 8u
+#define CTOK_PIPELINE_AT_NORMALIZED 16u /* stored by the reference, never read by encode */
+
+/* Strings are packed: string i = bytes[off[i] .. off[i + 1]).  The merges are the pairs that split
+ * into exactly two parts at ' ', in rank order: strings 2r and 2r + 1 are merge r's left and right. */
+typedef struct ctok_pipeline_tables {
+  const uint8_t* vocab_bytes;
+  const uint64_t* vocab_off;
+  const uint32_t* vocab_id;
+  uint64_t n_vocab;
+  const uint8_t* merge_bytes;
+  const uint64_t* merge_off;
+  uint64_t n_merge_strings;
+  const uint8_t* added_bytes;
+  const uint64_t* added_off;
+  const uint32_t* added_id;
+  const uint8_t* added_flags;
+  uint64_t n_added;
+} ctok_pipeline_tables;
+
+/* encode flags */
+#define CTOK_PIPELINE_TOKENIZE 1u /* tokenize (mod.rs:1080-1101): the word BPE without the added-token loop */
+
+/* nz and pt are borrowed (either may be NULL: no normaliser; the whole text is one word) and must
+ * outlive the handle and belong to `device`. */
+int ctok_pipeline_create(const ctok_pipeline_tables* tables, ctok_normalizer* nz, ctok_pretokenizer* pt, int device,
+                         ctok_pipeline** out);
+void ctok_pipeline_destroy(ctok_pipeline* p);
+
+/* n_texts host texts.  *ids (tok_off[n_texts] of them) and *tok_off (n_texts + 1) point into the
+ * handle and hold until its next call.  CTOK_E_ARG: a text is not UTF-8. */
+int ctok_pipeline_encode_batch(ctok_pipeline* p, const uint8_t* utf8, const uint64_t* off, uint64_t n_texts, uint32_t flags,
+                               const uint32_t** ids, const uint64_t** tok_off);
+
+/* Same, with every buffer resident in the device's memory and the work ordered on `stream` (a
+ * hipStream_t; NULL: the default stream); n_bytes = off[n_texts].  d_ids has room for ids_cap ids,
+ * d_tok_off for n_texts + 1.  d_off[0] must be 0 and d_off must not decrease (not checked: the offsets are
+ * device memory; without a normaliser and a pre-tokenizer they are the words' offsets as they stand, and
+ * n_bytes sizes the per-byte bitmaps).  The bytes are taken as they are: what is not well-formed UTF-8 is a
+ * unit in no vocab string, so it gives no id.  *n_ids_out receives the number of ids, also on
+ * CTOK_E_CAPACITY, when ids_cap is too small and nothing is written.  The call returns after the
+ * stream has finished the work. */
+int ctok_pipeline_encode_batch_device(ctok_pipeline* p, const uint8_t* d_utf8, const uint64_t* d_off, uint64_t n_texts,
+                                      uint64_t n_bytes, uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_tok_off,
+                                      uint64_t* n_ids_out, void* stream);
+
+/* The HIP-event time of each stage of the last call: normalize, pre_tokenize, segments, symbols,
+ * merges, emit. */
+#define CTOK_PIPELINE_STAGES 6
+int ctok_pipeline_stage_ms(const ctok_pipeline* p, double out[CTOK_PIPELINE_STAGES]);
+const char* ctok_pipeline_stage_name(uint64_t i); /* "" past the end */
+
+typedef struct ctok_pipeline_limits_t {
+  uint32_t tier1;                  /* symbols of a segment one thread merges */
+  uint32_t tier2;                  /* symbols of a segment one wavefront merges in LDS */
+  uint64_t max_word_symbols;       /* of this handle: CTOK_PIPELINE_MAX_WORD_SYMBOLS, read at create, may lower it */
+  uint64_t max_flagged_word_bytes; /* of this handle: bytes of a word that holds an added token */
+  uint64_t max_added_tokens;
+  uint64_t max_added_token_bytes;
+  uint64_t max_merges;
+  uint64_t max_added_group_bytes;  /* bytes of the added tokens that share a first byte */
+  uint64_t max_batch_bytes;        /* of this handle: bytes of words in one call (lower with added tokens, see above) */
+} ctok_pipeline_limits_t;
+/* p may be NULL: the built-in limits under the current environment */
+void ctok_pipeline_limits(const ctok_pipeline* p, ctok_pipeline_limits_t* out);
+
+/* What the last call did. */
+typedef struct ctok_pipeline_info {
+  uint64_t texts;
+  uint64_t bytes_in;
+  uint64_t bytes_normalized;
+  uint64_t bytes_words;
+  uint64_t words;
+  uint64_t segments;
+  uint64_t symbols;
+  uint64_t ids;
+  uint64_t tier2_segments;
+  uint64_t tier3_segments;
+  uint64_t max_segment_symbols;
+} ctok_pipeline_info;
+int ctok_pipeline_stats(const ctok_pipeline* p, ctok_pipeline_info* out);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* CTOK_PIPELINE_H */
