@@ -252,6 +252,29 @@ class PipelineLimits(ctypes.Structure):  # ctok_pipeline_limits_t
                 ("max_batch_bytes", ctypes.c_uint64)]
 
 
+class PipelineEncodings(ctypes.Structure):  # ctok_pipeline_encodings
+    _fields_ = [(k, ctypes.c_void_p) for k in ("ids", "type_ids", "special_tokens_mask", "row_off", "offsets", "word_ids", "seq_ids",
+                                               "seq_off", "n_a")] + [("n_rows", ctypes.c_uint64)]
+
+
+class PipelineEncodingsDevice(ctypes.Structure):  # ctok_pipeline_encodings_device
+    _fields_ = [("ids", ctypes.c_void_p), ("type_ids", ctypes.c_void_p), ("special_tokens_mask", ctypes.c_void_p),
+                ("cells_cap", ctypes.c_uint64), ("row_off", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("word_ids", ctypes.c_void_p),
+                ("seq_ids", ctypes.c_void_p), ("ids_cap", ctypes.c_uint64), ("seq_off", ctypes.c_void_p), ("n_a", ctypes.c_void_p), ("n_cells", ctypes.c_uint64),
+                ("n_ids", ctypes.c_uint64)]
+
+
+class PipelineEncodingLimits(ctypes.Structure):  # ctok_pipeline_encoding_limits_t
+    _fields_ = [("max_find_work", ctypes.c_uint64), ("max_special_tokens", ctypes.c_uint64), ("max_find_compares", ctypes.c_uint64)]
+
+
+class PipelineEncodingInfo(ctypes.Structure):  # ctok_pipeline_encoding_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("rows", "sequences", "words", "ids", "cells", "max_find_work")]
+
+
+CTOK_PIPELINE_ENCODING_STAGES = 3
+
+
 class PipelineInfo(ctypes.Structure):  # ctok_pipeline_info
     _fields_ = [(k, ctypes.c_uint64) for k in ("texts", "bytes_in", "bytes_normalized", "bytes_words", "words", "segments", "symbols",
                                                "ids", "tier2_segments", "tier3_segments", "max_segment_symbols")]
@@ -437,6 +460,13 @@ SIGS = {
     "ctok_pipeline_stage_name": (ctypes.c_char_p, [_u64]),
     "ctok_pipeline_limits": (None, [_p, ctypes.POINTER(PipelineLimits)]),
     "ctok_pipeline_stats": (ctypes.c_int, [_p, ctypes.POINTER(PipelineInfo)]),
+    "ctok_pipeline_encode_encodings": (ctypes.c_int, [_p, _p, _p, _u64, _p, _p, _p, ctypes.POINTER(PipelineEncodings)]),
+    "ctok_pipeline_encode_encodings_device": (ctypes.c_int, [_p, _p, _p, _u64, ctypes.c_int, _u64, _p,
+                                                             ctypes.POINTER(PipelineEncodingsDevice), _p]),
+    "ctok_pipeline_encoding_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double)]),
+    "ctok_pipeline_encoding_stage_name": (ctypes.c_char_p, [_u64]),
+    "ctok_pipeline_encoding_limits": (None, [_p, ctypes.POINTER(PipelineEncodingLimits)]),
+    "ctok_pipeline_encoding_stats": (ctypes.c_int, [_p, ctypes.POINTER(PipelineEncodingInfo)]),
 }
 
 for _name, (_res, _args) in SIGS.items():

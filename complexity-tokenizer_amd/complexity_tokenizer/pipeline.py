@@ -20,8 +20,9 @@ import json
 import numpy as np
 
 from . import _native as _n
-from . import _raise, _split_lists, pack_ids, pack_texts
+from . import _as_str, _as_str_list, _extract_str_list, _raise, _split_lists, _split_pairs, pack_ids, pack_texts
 from .decoders import Decoder
+from .encoding import BatchEncoding, Encoding
 from .models import _WHITE_SPACE
 from .normalizers import Normalizer
 from .postprocessors import PostProcessor
@@ -267,6 +268,8 @@ class PipelineTokenizer:
         self._decode_with = None
         self.device = device
         self.last_stats = None
+        self._model_max_length = 512  # from_tokenizer_json without a tokenizer_config.json (mod.rs:226)
+        self._padding_side = self._truncation_side = "right"  # mod.rs:325-326
         keys = [k.encode("utf-8") for k in self._vocab]
         ms = [s.encode("utf-8") for ab in merges for s in ab]
         ab = [t["content"].encode("utf-8") for t in self._added]
@@ -472,6 +475,239 @@ class PipelineTokenizer:
         if not isinstance(text, str):
             raise TypeError("'%s' object cannot be converted to 'PyString'" % type(text).__name__)
         return self.tokenize_batch([text])[0]
+
+    # ------------------------------------------------------------------ Encodings
+    # (src/bindings/tokenizer.rs:33-201, :259-367 -> src/huggingface/mod.rs:340-545).  Ids, offsets, word
+    # ids, type ids and the special mask of a whole batch come from one call of
+    # ctok_pipeline_encode_encodings; truncation and padding are Encoding's list methods.
+
+    @property
+    def model_max_length(self) -> int:
+        return self._model_max_length
+
+    @model_max_length.setter
+    def model_max_length(self, value: int):
+        if type(value) is not int or value < 0:
+            raise TypeError("model_max_length: expected a non-negative int")
+        self._model_max_length = value
+
+    @property
+    def padding_side(self) -> str:
+        return self._padding_side
+
+    @padding_side.setter
+    def padding_side(self, value: str):
+        self._padding_side = _as_str(value)
+
+    @property
+    def truncation_side(self) -> str:
+        """Stored and returned; the reference's truncation never reads it either."""
+        return self._truncation_side
+
+    @truncation_side.setter
+    def truncation_side(self, value: str):
+        self._truncation_side = _as_str(value)
+
+    @staticmethod
+    def encoding_limits(handle=None) -> dict:
+        lim = _n.PipelineEncodingLimits()
+        _n.lib.ctok_pipeline_encoding_limits(handle, ctypes.byref(lim))
+        return {k: int(getattr(lim, k)) for k, _ in lim._fields_}
+
+    def _read_encoding_stats(self):
+        self._read_stats()
+        ms = (ctypes.c_double * _n.CTOK_PIPELINE_ENCODING_STAGES)()
+        info = _n.PipelineEncodingInfo()
+        _n.lib.ctok_pipeline_encoding_stage_ms(self._h, ms)
+        _n.lib.ctok_pipeline_encoding_stats(self._h, ctypes.byref(info))
+        self.last_stats["encoding"] = {k: int(getattr(info, k)) for k, _ in info._fields_}
+        self.last_stats["encoding_stages"] = [(_n.lib.ctok_pipeline_encoding_stage_name(i).decode(), ms[i])
+                                              for i in range(_n.CTOK_PIPELINE_ENCODING_STAGES)]
+
+    def encode_encodings_flat(self, texts, pairs=None) -> dict:
+        """Extension: the batch's Encoding fields as flat arrays from one call on the GPU.  Row r is
+        texts[r] (and pairs[r]).  ids, type_ids, special_tokens_mask: uint32, row r at row_off[r] ..
+        row_off[r + 1] (the processed row); offsets uint64 [n, 2] and word_ids uint32 [n], row r at
+        seq_off[r] .. seq_off[r + 1] (one entry per id before the post-processor, seq_ids, each relative
+        to its own text); n_a[r] of them are texts[r]'s."""
+        texts = _as_str_list(texts)
+        text, off = pack_texts(texts)
+        rows = len(texts)
+        ptext = poff = None
+        if pairs is not None:
+            pairs = _as_str_list(pairs)
+            if len(pairs) != rows:
+                raise ValueError("pairs must have one entry per text")
+            ptext, poff = pack_texts(pairs)
+        out = _n.PipelineEncodings()
+        pp = self._post_processor._h if self._post_processor is not None else None
+        rc = _n.lib.ctok_pipeline_encode_encodings(self._h, text.ctypes.data, off.ctypes.data, rows,
+                                                   ptext.ctypes.data if ptext is not None else None,
+                                                   poff.ctypes.data if poff is not None else None, pp, ctypes.byref(out))
+        if rc:
+            _raise(rc)
+        self._read_encoding_stats()
+
+        def arr(ptr, ctype, dtype, n):
+            if not n:
+                return np.zeros(0, dtype=dtype)
+            return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=(n,)).copy()
+
+        row_off = arr(out.row_off, ctypes.c_uint64, np.uint64, rows + 1)
+        seq_off = arr(out.seq_off, ctypes.c_uint64, np.uint64, rows + 1)
+        cells, n = int(row_off[rows]), int(seq_off[rows])
+        return {"ids": arr(out.ids, ctypes.c_uint32, np.uint32, cells), "type_ids": arr(out.type_ids, ctypes.c_uint32, np.uint32, cells),
+                "special_tokens_mask": arr(out.special_tokens_mask, ctypes.c_uint32, np.uint32, cells), "row_off": row_off,
+                "offsets": arr(out.offsets, ctypes.c_uint64, np.uint64, 2 * n).reshape(-1, 2),
+                "word_ids": arr(out.word_ids, ctypes.c_uint32, np.uint32, n), "seq_ids": arr(out.seq_ids, ctypes.c_uint32, np.uint32, n),
+                "seq_off": seq_off,
+                "n_a": arr(out.n_a, ctypes.c_uint64, np.uint64, rows)}
+
+    def encode_encodings_device(self, d_text: int, d_off: int, n_rows: int, n_bytes: int, *, d_ids: int, d_type_ids: int, d_special: int,
+                                cells_cap: int, d_row_off: int, d_offsets: int, d_word_ids: int, ids_cap: int, d_seq_off: int, d_n_a: int,
+                                d_seq_ids: int = 0, pairs: bool = False, stream: int = 0):
+        """Extension: the same over raw device pointers (ints; e.g. torch tensors' data_ptr()) of this
+        tokenizer's device, ordered on the HIP stream `stream` (0: the default stream).  With pairs the
+        sequences are interleaved: 2r is row r's text, 2r + 1 its pair, and d_off has 2 * n_rows + 1
+        entries.  d_ids, d_type_ids and d_special hold cells_cap uint32, d_offsets 2 * ids_cap uint64,
+        d_word_ids and d_seq_ids (0: not wanted) ids_cap uint32, d_row_off and d_seq_off n_rows + 1 uint64, d_n_a n_rows uint64.
+        Returns (cells, ids); raises BufferError carrying `.needed` = (cells, ids) when a capacity is too
+        small, with nothing written.  The bytes are taken as they are.  Returns after the work is done."""
+        out = _n.PipelineEncodingsDevice(d_ids or None, d_type_ids or None, d_special or None, cells_cap, d_row_off or None,
+                                         d_offsets or None, d_word_ids or None, d_seq_ids or None, ids_cap, d_seq_off or None, d_n_a or None, 0, 0)
+        pp = self._post_processor._h if self._post_processor is not None else None
+        rc = _n.lib.ctok_pipeline_encode_encodings_device(self._h, d_text or None, d_off or None, n_rows, 1 if pairs else 0, n_bytes, pp,
+                                                          ctypes.byref(out), stream or None)
+        if rc == _n.CTOK_E_CAPACITY and (out.n_cells > cells_cap or out.n_ids > ids_cap):
+            e = BufferError("encode_encodings_device: %d cells and %d ids are needed, the capacities are %d and %d"
+                            % (out.n_cells, out.n_ids, cells_cap, ids_cap))
+            e.needed = (int(out.n_cells), int(out.n_ids))
+            raise e
+        if rc:
+            _raise(rc)
+        self._read_encoding_stats()
+        return int(out.n_cells), int(out.n_ids)
+
+    def _pad_id_token(self):
+        """mod.rs:505-510"""
+        pid = self._special.get("[PAD]", self._special.get("<pad>", 0))
+        return pid, self._id_to_token.get(pid, "<pad>")
+
+    def _to_encodings(self, texts, pairs=None, add_special_tokens=True) -> list:
+        """Encodings before truncation and padding: encode_to_encoding / encode_pair_to_encoding
+        (mod.rs:340-392), or with add_special_tokens=False Encoding::from_ids over encode() (+ merge for a
+        pair, src/bindings/tokenizer.rs:64-97): no offsets, no word ids, and `tokens` without the ids that
+        have no vocab string.  One GPU call either way."""
+        names = self._id_to_token
+        rows = len(texts)
+        if not add_special_tokens:
+            docs = [x for ab in zip(texts, pairs) for x in ab] if pairs is not None else list(texts)
+            ids, tok_off = self.encode_batch_flat(docs)
+            ids, o = ids.tolist(), tok_off.tolist()
+            k = 2 if pairs is not None else 1
+            encs = []
+            for r in range(rows):
+                a, m, b = o[k * r], o[k * r + 1], o[k * r + k]
+                row = ids[a:b]
+                types = [0] * (m - a) + [1] * (b - m)
+                encs.append(Encoding(row, types, [names[i] for i in row if i in names], [1] * (b - a), [0] * (b - a), [], [], list(types)))
+            return encs
+        f = self.encode_encodings_flat(texts, pairs)
+        ids, types, special = f["ids"].tolist(), f["type_ids"].tolist(), f["special_tokens_mask"].tolist()
+        offsets, wids = f["offsets"].tolist(), f["word_ids"].tolist()
+        ro, so, na = f["row_off"].tolist(), f["seq_off"].tolist(), f["n_a"].tolist()
+        flat = f["seq_ids"].tolist()
+        encs = []
+        for r in range(rows):
+            a, b, c, d = ro[r], ro[r + 1], so[r], so[r + 1]
+            n = d - c
+            # one token string per id before the post-processor, "" outside the vocab (mod.rs:410); the
+            # post-processor extends neither tokens nor offsets, word ids and sequence ids (mod.rs:378-386)
+            toks = [names.get(i, "") for i in flat[c:d]]
+            encs.append(Encoding(ids[a:b], types[a:b], toks, [1] * (b - a), special[a:b], [tuple(x) for x in offsets[c:d]], wids[c:d],
+                                 [0] * na[r] + [1] * (n - na[r])))
+        return encs
+
+    def encode_to_encoding(self, text: str) -> Encoding:
+        """src/bindings/tokenizer.rs:298-300 -> mod.rs:340-342"""
+        return self._to_encodings([_as_str(text)])[0]
+
+    def encode_plus(self, text: str) -> Encoding:
+        """src/bindings/tokenizer.rs:258-260"""
+        return self.encode_to_encoding(text)
+
+    def encode_pair_to_encoding(self, text: str, text_pair: str) -> Encoding:
+        """src/bindings/tokenizer.rs:302-304 -> mod.rs:344-346"""
+        return self._to_encodings([_as_str(text)], [_as_str(text_pair)])[0]
+
+    def encode_with_truncation(self, text: str, text_pair: str | None = None, max_length: int = 512, stride: int = 0) -> Encoding:
+        """src/bindings/tokenizer.rs:306-318 -> mod.rs:348-392"""
+        enc = self.encode_pair_to_encoding(text, text_pair) if text_pair is not None else self.encode_to_encoding(text)
+        if len(enc) > max_length:
+            enc.truncate_with_stride(max_length, stride)
+        return enc
+
+    def encode_batch_to_encoding(self, texts) -> list:
+        """src/bindings/tokenizer.rs:320-326 -> mod.rs:483-485"""
+        return self._to_encodings(_as_str_list(texts))
+
+    def batch_encode_plus(self, texts) -> list:
+        """src/bindings/tokenizer.rs:262-269"""
+        return self.encode_batch_to_encoding(texts)
+
+    def encode_batch_pairs_to_encoding(self, pairs) -> list:
+        """src/bindings/tokenizer.rs:328-336 -> mod.rs:487-491"""
+        a, b = _split_pairs(pairs)
+        return self._to_encodings(a, b)
+
+    def _pad_all(self, encs, max_length, pad_left):
+        target = max_length if max_length is not None else max((len(e) for e in encs), default=0)
+        pid, ptok = self._pad_id_token()
+        for e in encs:
+            e.pad(target, pid, ptok, pad_left)
+        return encs
+
+    def encode_batch_with_padding(self, texts, max_length: int | None = None, pad_left: bool = False) -> list:
+        """src/bindings/tokenizer.rs:338-350 -> mod.rs:493-517 (no truncation)"""
+        return self._pad_all(self.encode_batch_to_encoding(texts), max_length, pad_left)
+
+    def encode_batch_pairs_with_padding(self, pairs, max_length: int | None = None, pad_left: bool = False) -> list:
+        """src/bindings/tokenizer.rs:352-367 -> mod.rs:519-543"""
+        return self._pad_all(self.encode_batch_pairs_to_encoding(pairs), max_length, pad_left)
+
+    def __call__(self, text, text_pair=None, add_special_tokens: bool = True, padding: str | None = None, truncation: bool = False,
+                 max_length: int | None = None, stride: int = 0, return_attention_mask: bool = True, return_token_type_ids: bool = True,
+                 return_offsets_mapping: bool = False, return_special_tokens_mask: bool = False) -> BatchEncoding:
+        """src/bindings/tokenizer.rs:33-201"""
+        flags = (return_attention_mask, return_token_type_ids, return_offsets_mapping, return_special_tokens_mask)
+        max_len = max_length if max_length is not None else self._model_max_length
+        batch = _extract_str_list(text)
+        if batch is not None:
+            pairs = _extract_str_list(text_pair) if text_pair is not None else None
+            if pairs is not None:
+                m = min(len(batch), len(pairs))  # Iterator::zip
+                batch, pairs = batch[:m], pairs[:m]
+            encs = self._to_encodings(batch, pairs, add_special_tokens)
+        elif isinstance(text, str):
+            pair = text_pair if isinstance(text_pair, str) else None
+            encs = self._to_encodings([text], [pair] if pair is not None else None, add_special_tokens)
+        else:
+            raise TypeError("Expected str or List[str]")
+        if truncation:
+            for e in encs:
+                if len(e) > max_len:
+                    if stride > 0:
+                        e.truncate_with_stride(max_len, stride)
+                    else:
+                        e.truncate(max_len)
+        if padding is not None:
+            # (a str input pads to its own length: the longest of a batch of one)
+            target = max_len if padding == "max_length" else max((len(e) for e in encs), default=0)
+            pid, ptok = self._pad_id_token()
+            left = padding == "left" or self._padding_side == "left"
+            for e in encs:
+                e.pad(target, pid, ptok, left)
+        return BatchEncoding(encs, *flags)
 
     # ------------------------------------------------------------------ decode
     def _decoder_with_vocab(self):

@@ -13,6 +13,8 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <functional>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -22,6 +24,7 @@
 #include "gen/alnum_data.h"
 #include "host_common.h"
 #include "knobs.h"
+#include "pipeline_enc_internal.h"
 #include "train_host_common.h"
 #include "wordbpe_compile.h"
 #include "wordbpe_internal.h"
@@ -39,6 +42,14 @@ namespace {
 constexpr uint64_t kRefuseFrom = 0xFFFFFF00ull;  // bytes, words or texts of one call: 4 GiB less the slack of the u32 scans
 
 const char* const kStageNames[CTOK_PIPELINE_STAGES] = {"normalize", "pre_tokenize", "segments", "symbols", "merges", "emit"};
+
+const char* const kEncStageNames[CTOK_PIPELINE_ENCODING_STAGES] = {"find", "spans", "rows"};
+
+uint64_t find_work_cap() {
+  uint64_t cap = ctok_pe::kMaxFindWork;
+  if (auto e = ctok_rt::env_u64("CTOK_PIPELINE_MAX_FIND_WORK")) cap = std::min<uint64_t>(cap, *e);
+  return cap;
+}
 
 uint64_t word_cap() {
   uint64_t cap = kMaxWordSymbols;
@@ -77,8 +88,21 @@ struct ctok_pipeline {
   uint64_t match_cap = ~0ull;                // bytes of a batch the filter pass takes
   hipStream_t own = nullptr;
   hipEvent_t ev[CTOK_PIPELINE_STAGES + 1] = {};
+  hipEvent_t ev_merge = nullptr;  // the merges begin: after the counts of the symbols stage came back
   double stage_ms[CTOK_PIPELINE_STAGES] = {};
   ctok_pipeline_info info{};
+  // the Encoding path (pipeline_enc.hip)
+  uint64_t find_cap = ctok_pe::kMaxFindWork;
+  hipEvent_t ev_enc[2 * CTOK_PIPELINE_ENCODING_STAGES] = {};  // begin and end of find, spans, rows
+  double enc_ms[CTOK_PIPELINE_ENCODING_STAGES] = {};
+  ctok_pipeline_encoding_info enc_info{};
+  std::vector<uint32_t> len_id, len_val, special_id;  // id -> bytes of its vocab string; the special added tokens' ids
+  DBuf<uint32_t> d_len_id, d_len_val, d_special;
+  DBuf<uint64_t> wstart, wend, work, rep, lens, tmp64, e_off, e_seq_off, e_na, e_row_off;
+  DBuf<uint32_t> e_wids, e_out, e_type, e_spec;
+  std::vector<uint8_t> h_text;
+  std::vector<uint64_t> h_off, h_row_off, h_seq_off, h_na, h_offsets;
+  std::vector<uint32_t> h_out, h_type, h_spec, h_wids, h_seq_ids;
   // the tables
   DBuf<wordbpe::CpSlot> d_cps;
   DBuf<strmerge::PairSlot> d_pairs;
@@ -91,6 +115,8 @@ struct ctok_pipeline {
   DBuf<uint32_t> wbits, mbits, kbits, kpc, krank, wseg, segoff, nsym, soff, fcnt, wpos, sym, list2, list3, state, ctr, tmp, ids;
   DBuf<wordbpe::Seg> segs;
   Batch B{};
+  uint32_t n2 = 0, n3 = 0, n_sym_run = 0;  // between the two phases of a run
+  uint64_t n_state = 0;
   uint64_t n_ids = 0;
   std::vector<uint32_t> h_ids;
   std::vector<uint64_t> h_tok_off;
@@ -98,6 +124,9 @@ struct ctok_pipeline {
   ~ctok_pipeline() {
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_enc)
+      if (e) (void)hipEventDestroy(e);
+    if (ev_merge) (void)hipEventDestroy(ev_merge);
     if (own) (void)hipStreamDestroy(own);
   }
 
@@ -110,6 +139,11 @@ struct ctok_pipeline {
     HIPT(hipSetDevice(device));
     HIPT(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
     for (auto& e : ev) HIPT(hipEventCreate(&e));
+    for (auto& e : ev_enc) HIPT(hipEventCreate(&e));
+    HIPT(hipEventCreate(&ev_merge));
+    upload(d_len_id, len_id.data(), len_id.size(), own);
+    upload(d_len_val, len_val.data(), len_val.size(), own);
+    upload(d_special, special_id.data(), special_id.size(), own);
     upload(d_cps, c.cps.data(), c.cps.size(), own);
     upload(d_pairs, c.pairs.data(), c.pairs.size(), own);
     upload(d_abytes, c.a_bytes.data(), c.a_bytes.size(), own);
@@ -146,6 +180,12 @@ struct ctok_pipeline {
 
   // Everything up to the count of the ids (n_ids); emit() writes them.  n > 0.
   void run(const uint8_t* d_text, const uint64_t* d_off, uint64_t n, uint64_t nb, uint32_t flags, hipStream_t s) {
+    run_words(d_text, d_off, n, nb, flags, s);
+    run_merges(s, nullptr);
+  }
+
+  // The first phase: the words, their segments and symbols, and every refusal of a segment's size.
+  void run_words(const uint8_t* d_text, const uint64_t* d_off, uint64_t n, uint64_t nb, uint32_t flags, hipStream_t s) {
     HIPT(hipSetDevice(device));
     for (double& t : stage_ms) t = 0;
     info = ctok_pipeline_info{};
@@ -291,8 +331,9 @@ struct ctok_pipeline {
     uint32_t h_ctr[kNumCtr] = {};
     HIPT(hipMemcpyAsync(h_ctr, ctr.p, kNumCtr * 4, hipMemcpyDeviceToHost, s));
     HIPT(hipStreamSynchronize(s));
-    const uint32_t n2 = h_ctr[kCtrList2], n3 = h_ctr[kCtrList3];
-    const uint64_t n_state = (uint64_t)h_ctr[kCtrState] | (uint64_t)h_ctr[kCtrState + 1] << 32;
+    n2 = h_ctr[kCtrList2], n3 = h_ctr[kCtrList3];
+    n_state = (uint64_t)h_ctr[kCtrState] | (uint64_t)h_ctr[kCtrState + 1] << 32;
+    n_sym_run = n_sym;
     if (n2 > cap2 || n3 > cap3 || n_state > n_sym) throw_error(CTOK_E_DEVICE, "pipeline: the segment list is out of bounds");
     info.symbols = n_sym;
     info.tier2_segments = n2;
@@ -302,8 +343,14 @@ struct ctok_pipeline {
       throw_error(CTOK_E_UNSUPPORTED, "a word of " + std::to_string(h_ctr[kCtrMaxSym]) + " symbols: the merge loop is quadratic "
                                           "in a word's length, words of more than " + std::to_string(cap) +
                                           " symbols are not supported");
+  }
 
+  // The second phase: the merges and the count of the ids.  before_panic (may be null) sees the segment of
+  // a merge panic before it is reported, and may report something that comes first instead.
+  void run_merges(hipStream_t s, const std::function<void(uint32_t)>* before_panic) {
+    const uint32_t n_segs = B.n_segs, n_sym = n_sym_run;
     // 5. the merges
+    HIPT(hipEventRecord(ev_merge, s));
     state.ensure(4 * n_state + 1);
     B.state = state.p;
     HIPT(launch_merge(T, B, n2, n3, s));
@@ -315,6 +362,7 @@ struct ctok_pipeline {
       const uint32_t at = read_u32(soff.p + panic_seg, s);
       if (at >= n_sym) throw_error(CTOK_E_DEVICE, "pipeline: the panic report is out of bounds");
       const uint32_t rank = read_u32(sym.p + at, s);
+      if (before_panic) (*before_panic)(panic_seg);
       throw_error(CTOK_E_PANIC, "index out of bounds: the len is " + std::to_string(c.n_filtered) + " but the index is " +
                                     std::to_string(rank));
     }
@@ -329,9 +377,158 @@ struct ctok_pipeline {
     HIPT(hipStreamSynchronize(s));
     for (int i = 0; i < CTOK_PIPELINE_STAGES; i++) {
       float ms = 0;
-      HIPT(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      HIPT(hipEventElapsedTime(&ms, i == 4 ? ev_merge : ev[i], ev[i + 1]));
       stage_ms[i] = ms;
     }
+  }
+
+  // ---- the Encoding path (include/ctok_pipeline.h, "Encodings") ----------------------------------------
+  uint64_t h_rep0[ctok_pe::kNumRep] = {ctok_pe::kNoPanic, 0, ~0ull, ~0ull, ~0ull};
+  uint64_t n_cells = 0;
+  const uint32_t* r_ids = nullptr;      // the processed ids and their rows: the post-processor's, or the ids as they are
+  const uint64_t* r_row_off = nullptr;
+
+  [[noreturn]] static void throw_boundary(uint64_t report) {
+    throw_error(CTOK_E_PANIC, "byte index " + std::to_string(report & 0xFFFFFFFFull) + " is not a char boundary");
+  }
+
+  // n_rows * per_row sequences (row r: sequences r * per_row ..) through tokenize, the word search, the
+  // token spans, the post-processor and the row masks.  Everything stays in the handle's buffers.  The
+  // errors in order: the refusals (4 GiB, word symbols, find work), then of the panics the lowest
+  // sequence's, the char boundary before the merge, and the subtraction last.  n_rows > 0.
+  void encodings(const uint8_t* d_text, const uint64_t* d_off, uint64_t n_rows, uint32_t per_row, uint64_t nb, ctok_postprocessor* pp,
+                 hipStream_t s) {
+    using namespace ctok_pe;
+    const uint64_t n = n_rows * per_row;
+    for (double& t : enc_ms) t = 0;
+    enc_info = ctok_pipeline_encoding_info{};
+    enc_info.rows = n_rows;
+    enc_info.sequences = n;
+    run_words(d_text, d_off, n, nb, CTOK_PIPELINE_TOKENIZE, s);
+    const uint64_t n_words = B.n_words;
+    if (B.n_segs != n_words) throw_error(CTOK_E_DEVICE, "pipeline: tokenize has a segment per word");
+    enc_info.words = n_words;
+
+    // the words' spans
+    wstart.ensure(n_words + 1);
+    wend.ensure(n_words + 1);
+    work.ensure(n + 1);
+    rep.ensure(kNumRep);
+    HIPT(hipMemcpyAsync(rep.p, h_rep0, sizeof(h_rep0), hipMemcpyHostToDevice, s));
+    const Find f{d_text, d_off, n, B.text, B.word_off, B.text_word, n_words, wstart.p, wend.p, work.p, (unsigned long long*)rep.p, find_cap,
+                 find_cap / kFindCompareShare};
+    HIPT(hipEventRecord(ev_enc[0], s));
+    HIPT(launch_word_find(f, s));
+    HIPT(hipEventRecord(ev_enc[1], s));
+    uint64_t h_rep[kNumRep] = {};
+    HIPT(hipMemcpyAsync(h_rep, rep.p, sizeof(h_rep), hipMemcpyDeviceToHost, s));
+    HIPT(hipStreamSynchronize(s));
+    enc_info.max_find_work = h_rep[kRepMaxWork];
+    if (h_rep[kRepOver] != ~0ull) {
+      const uint64_t q = h_rep[kRepOver];
+      if (q >= n) throw_error(CTOK_E_DEVICE, "pipeline: the work report is out of bounds");
+      uint64_t w = 0;
+      HIPT(hipMemcpyAsync(&w, work.p + q, 8, hipMemcpyDeviceToHost, s));
+      HIPT(hipStreamSynchronize(s));
+      throw_error(CTOK_E_UNSUPPORTED, "sequence " + std::to_string(q) + " (row " + std::to_string(q / per_row) +
+                                          (per_row == 2 ? (q & 1 ? ", the pair" : ", the text") : "") + "): the search for its words' offsets has work " +
+                                          std::to_string(w) + ", one wavefront walks a sequence and a word that is not found scans to the text's end; "
+                                          "work of more than " + std::to_string(find_cap) + " is not supported");
+    }
+    if (h_rep[kRepCompares] != ~0ull) {
+      const uint64_t q = h_rep[kRepCompares];
+      throw_error(CTOK_E_UNSUPPORTED, "sequence " + std::to_string(q) + " (row " + std::to_string(q / per_row) +
+                                          (per_row == 2 ? (q & 1 ? ", the pair" : ", the text") : "") +
+                                          "): the search for its words' offsets compares more than " +
+                                          std::to_string(find_cap / kFindCompareShare) +
+                                          " bytes of partial matches at one position in 64, which is not supported");
+    }
+    const uint64_t find_panic = h_rep[kRepPanic];
+    if (find_panic != kNoPanic && (find_panic >> 32) >= n) throw_error(CTOK_E_DEVICE, "pipeline: the panic report is out of bounds");
+
+    // the merges; a merge panic is reported unless the char-boundary panic is the same or a lower sequence's
+    const std::function<void(uint32_t)> before_merge_panic = [&](uint32_t word) {
+      if (find_panic == kNoPanic) return;
+      std::vector<uint64_t> tw(n + 1);
+      HIPT(hipMemcpyAsync(tw.data(), B.text_word, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIPT(hipStreamSynchronize(s));
+      const uint64_t q = (uint64_t)(std::upper_bound(tw.begin(), tw.end(), (uint64_t)word) - tw.begin()) - 1;
+      if ((find_panic >> 32) <= q) throw_boundary(find_panic);
+    };
+    run_merges(s, &before_merge_panic);
+    if (find_panic != kNoPanic) throw_boundary(find_panic);
+    ids.ensure(n_ids + 1);
+    tok_off.ensure(n + 1);
+    emit(ids.p, tok_off.p, s);
+    enc_info.ids = n_ids;
+
+    // the token spans
+    lens.ensure(n_ids + 2);
+    e_off.ensure(2 * n_ids + 2);
+    e_wids.ensure(n_ids + 1);
+    tmp64.ensure(ctok_dev::scan_tmp_elems(n_ids + 1) + 64);
+    const Spans sp{ids.p, n_ids, lens.p, d_len_id.p, d_len_val.p, (uint32_t)len_id.size(), wpos.p, (uint32_t)n_words, B.text_word, n,
+                   wstart.p, wend.p, e_off.p, e_wids.p};
+    HIPT(hipEventRecord(ev_enc[2], s));
+    HIPT(launch_tok_len(sp, s));
+    if (n_ids) HIPT(ctok_dev::scan_u64(lens.p, n_ids, tmp64.p, tmp64.cap, s));
+    HIPT(launch_tok_spans(sp, s));
+    HIPT(hipEventRecord(ev_enc[3], s));
+
+    // the rows
+    e_seq_off.ensure(n_rows + 1);
+    e_na.ensure(n_rows + 1);
+    Rows r{};
+    r.tok_off = tok_off.p;
+    r.per_row = per_row;
+    r.n_rows = n_rows;
+    r.seq_off = e_seq_off.p;
+    r.n_a = e_na.p;
+    r.special = d_special.p;
+    r.n_special = (uint32_t)special_id.size();
+    r.rep = (unsigned long long*)rep.p;
+    HIPT(hipEventRecord(ev_enc[4], s));
+    HIPT(launch_row_heads(r, s));
+    r_ids = ids.p;
+    r_row_off = e_seq_off.p;
+    n_cells = n_ids;
+    if (pp) {
+      e_row_off.ensure(n_rows + 1);
+      e_out.ensure(n_ids + 4 * n_rows + 64);
+      ctok_pp_batch in{};
+      in.ids = ids.p;
+      in.off = e_seq_off.p;
+      in.n_rows = n_rows;
+      uint64_t need = 0;
+      int rc = ctok_postprocessor_run_device(pp, &in, n_ids, 0, nullptr, e_out.p, e_out.cap, e_row_off.p, &need, s);
+      if (rc == CTOK_E_CAPACITY && need > e_out.cap) {
+        e_out.ensure(need + 1);
+        rc = ctok_postprocessor_run_device(pp, &in, n_ids, 0, nullptr, e_out.p, e_out.cap, e_row_off.p, &need, s);
+      }
+      if (rc) rethrow(rc);
+      r_ids = e_out.p;
+      r_row_off = e_row_off.p;
+      n_cells = need;
+    }
+    enc_info.cells = n_cells;
+    e_type.ensure(n_cells + 1);
+    e_spec.ensure(n_cells + 1);
+    r.out_ids = r_ids;
+    r.row_off = r_row_off;
+    r.n_cells = n_cells;
+    r.type_ids = e_type.p;
+    r.special_mask = e_spec.p;
+    HIPT(launch_enc_rows(r, s));
+    HIPT(hipEventRecord(ev_enc[5], s));
+    uint64_t short_row = 0;
+    HIPT(hipMemcpyAsync(&short_row, rep.p + kRepShort, 8, hipMemcpyDeviceToHost, s));
+    HIPT(hipStreamSynchronize(s));
+    for (int i = 0; i < CTOK_PIPELINE_ENCODING_STAGES; i++) {
+      float ms = 0;
+      HIPT(hipEventElapsedTime(&ms, ev_enc[2 * i], ev_enc[2 * i + 1]));
+      enc_ms[i] = ms;
+    }
+    if (short_row != ~0ull) throw_error(CTOK_E_PANIC, "attempt to subtract with overflow");
   }
 };
 
@@ -382,6 +579,26 @@ int ctok_pipeline_create(const ctok_pipeline_tables* tb, ctok_normalizer* nz, ct
     p->pt = pt;
     p->device = device;
     p->cap = word_cap();
+    p->find_cap = find_work_cap();
+    // id -> the bytes of its vocab string: of the strings that share an id the last one, which is what
+    // id_to_token answers; ids need not be dense, so a sorted table
+    {
+      std::vector<std::pair<uint32_t, uint32_t>> il;
+      il.reserve(vocab.size());
+      for (const auto& kv : vocab) il.emplace_back(kv.second, (uint32_t)std::min<size_t>(kv.first.size(), 0xFFFFFFFFu));
+      std::stable_sort(il.begin(), il.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+      for (size_t i = 0; i < il.size(); i++) {
+        if (i + 1 < il.size() && il[i + 1].first == il[i].first) continue;
+        p->len_id.push_back(il[i].first);
+        p->len_val.push_back(il[i].second);
+      }
+      std::map<std::string, uint32_t> special;  // content -> id as the reference's map keeps it: the last entry of a content
+      for (uint64_t i = 0; i < as.size(); i++)
+        if (tb->added_flags[i] & CTOK_PIPELINE_AT_SPECIAL) special[as[i]] = tb->added_id[i];
+      for (const auto& kv : special) p->special_id.push_back(kv.second);
+      std::sort(p->special_id.begin(), p->special_id.end());
+      p->special_id.erase(std::unique(p->special_id.begin(), p->special_id.end()), p->special_id.end());
+    }
     std::string err;
     const int rc = wordbpe::compile(vocab, merges, added, &p->c, &err);
     if (rc != wordbpe::kOk) throw_error(rc, err);
@@ -448,6 +665,147 @@ int ctok_pipeline_encode_batch_device(ctok_pipeline* p, const uint8_t* d_utf8, c
       throw_error(CTOK_E_CAPACITY, "ctok_pipeline_encode_batch_device: the ids need " + std::to_string(p->n_ids) + " entries");
     if (p->n_ids && !d_ids) throw_error(CTOK_E_ARG, "null argument");
     p->emit(d_ids, d_tok_off, s);
+  });
+}
+
+int ctok_pipeline_encode_encodings(ctok_pipeline* p, const uint8_t* utf8, const uint64_t* off, uint64_t n_rows, const uint8_t* pair_utf8,
+                                   const uint64_t* pair_off, ctok_postprocessor* pp, ctok_pipeline_encodings* out) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !out || (n_rows && (!off || (off[n_rows] && !utf8)))) throw_error(CTOK_E_ARG, "null argument");
+    if (pair_off && n_rows && pair_off[n_rows] && !pair_utf8) throw_error(CTOK_E_ARG, "null argument");
+    const uint32_t per_row = pair_off ? 2 : 1;
+    p->h_out.clear(), p->h_type.clear(), p->h_spec.clear(), p->h_wids.clear(), p->h_seq_ids.clear(), p->h_offsets.clear(), p->h_na.assign(n_rows, 0);
+    p->h_row_off.assign(n_rows + 1, 0);
+    p->h_seq_off.assign(n_rows + 1, 0);
+    *out = ctok_pipeline_encodings{p->h_out.data(), p->h_type.data(), p->h_spec.data(), p->h_row_off.data(), p->h_offsets.data(),
+                                   p->h_wids.data(), p->h_seq_ids.data(), p->h_seq_off.data(), p->h_na.data(), n_rows};
+    for (double& t : p->stage_ms) t = 0;
+    for (double& t : p->enc_ms) t = 0;
+    if (!n_rows) return;
+    if (off[0] != 0 || (pair_off && pair_off[0] != 0)) throw_error(CTOK_E_ARG, "offsets[0] must be 0");
+    for (uint64_t i = 0; i < n_rows; i++) {
+      if (off[i] > off[i + 1] || (pair_off && pair_off[i] > pair_off[i + 1])) throw_error(CTOK_E_ARG, "offsets must not decrease");
+      if (!valid_utf8(utf8, off[i], off[i + 1])) throw_error(CTOK_E_ARG, "text " + std::to_string(i) + " is not UTF-8");
+      if (pair_off && !valid_utf8(pair_utf8, pair_off[i], pair_off[i + 1]))
+        throw_error(CTOK_E_ARG, "pair text " + std::to_string(i) + " is not UTF-8");
+    }
+    const uint64_t nb = off[n_rows] + (pair_off ? pair_off[n_rows] : 0), n = n_rows * per_row;
+    if (nb >= kRefuseFrom || n >= kRefuseFrom) throw_error(CTOK_E_CAPACITY, "pipeline: the input reaches 4 GiB");
+    // the sequences in row order: 2r is row r's text, 2r + 1 its pair
+    const uint8_t* text = utf8;
+    const uint64_t* toff = off;
+    if (pair_off) {
+      p->h_text.resize(nb);
+      p->h_off.resize(n + 1);
+      uint64_t at = 0;
+      for (uint64_t i = 0; i < n_rows; i++) {
+        p->h_off[2 * i] = at;
+        if (off[i + 1] > off[i]) std::copy(utf8 + off[i], utf8 + off[i + 1], p->h_text.begin() + at);
+        at += off[i + 1] - off[i];
+        p->h_off[2 * i + 1] = at;
+        if (pair_off[i + 1] > pair_off[i]) std::copy(pair_utf8 + pair_off[i], pair_utf8 + pair_off[i + 1], p->h_text.begin() + at);
+        at += pair_off[i + 1] - pair_off[i];
+      }
+      p->h_off[n] = at;
+      text = p->h_text.data();
+      toff = p->h_off.data();
+    }
+    HIPT(hipSetDevice(p->device));
+    hipStream_t s = p->own;
+    p->in_text.ensure(nb + 64);
+    p->in_off.ensure(n + 1);
+    if (nb) HIPT(hipMemcpyAsync(p->in_text.p, text, nb, hipMemcpyHostToDevice, s));
+    HIPT(hipMemcpyAsync(p->in_off.p, toff, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    p->encodings(p->in_text.p, p->in_off.p, n_rows, per_row, nb, pp, s);
+    const uint64_t ni = p->n_ids, nc = p->n_cells;
+    p->h_out.resize(nc), p->h_type.resize(nc), p->h_spec.resize(nc), p->h_wids.resize(ni), p->h_seq_ids.resize(ni), p->h_offsets.resize(2 * ni);
+    if (nc) {
+      HIPT(hipMemcpyAsync(p->h_out.data(), p->r_ids, nc * 4, hipMemcpyDeviceToHost, s));
+      HIPT(hipMemcpyAsync(p->h_type.data(), p->e_type.p, nc * 4, hipMemcpyDeviceToHost, s));
+      HIPT(hipMemcpyAsync(p->h_spec.data(), p->e_spec.p, nc * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (ni) {
+      HIPT(hipMemcpyAsync(p->h_wids.data(), p->e_wids.p, ni * 4, hipMemcpyDeviceToHost, s));
+      HIPT(hipMemcpyAsync(p->h_seq_ids.data(), p->ids.p, ni * 4, hipMemcpyDeviceToHost, s));
+      HIPT(hipMemcpyAsync(p->h_offsets.data(), p->e_off.p, ni * 16, hipMemcpyDeviceToHost, s));
+    }
+    HIPT(hipMemcpyAsync(p->h_row_off.data(), p->r_row_off, (n_rows + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPT(hipMemcpyAsync(p->h_seq_off.data(), p->e_seq_off.p, (n_rows + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPT(hipMemcpyAsync(p->h_na.data(), p->e_na.p, n_rows * 8, hipMemcpyDeviceToHost, s));
+    HIPT(hipStreamSynchronize(s));
+    *out = ctok_pipeline_encodings{p->h_out.data(), p->h_type.data(), p->h_spec.data(), p->h_row_off.data(), p->h_offsets.data(),
+                                   p->h_wids.data(), p->h_seq_ids.data(), p->h_seq_off.data(), p->h_na.data(), n_rows};
+  });
+}
+
+int ctok_pipeline_encode_encodings_device(ctok_pipeline* p, const uint8_t* d_utf8, const uint64_t* d_off, uint64_t n_rows, int pairs,
+                                          uint64_t nb, ctok_postprocessor* pp, ctok_pipeline_encodings_device* out, void* stream) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !out || !out->row_off || !out->seq_off || (n_rows && (!d_off || !out->n_a)) || (nb && !d_utf8))
+      throw_error(CTOK_E_ARG, "null argument");
+    out->n_cells = out->n_ids = 0;
+    // checked before any device is used: a refused call launches nothing and writes nothing
+    if (((uintptr_t)out->ids | (uintptr_t)out->type_ids | (uintptr_t)out->special_tokens_mask | (uintptr_t)out->word_ids | (uintptr_t)out->seq_ids) & 3u)
+      throw_error(CTOK_E_ARG, "ctok_pipeline_encode_encodings_device: the ids must be 4-byte aligned");
+    if (((uintptr_t)d_off | (uintptr_t)out->row_off | (uintptr_t)out->seq_off | (uintptr_t)out->n_a | (uintptr_t)out->offsets) & 7u)
+      throw_error(CTOK_E_ARG, "ctok_pipeline_encode_encodings_device: the offsets must be 8-byte aligned");
+    HIPT(hipSetDevice(p->device));
+    hipStream_t s = (hipStream_t)stream;
+    for (double& t : p->stage_ms) t = 0;
+    for (double& t : p->enc_ms) t = 0;
+    if (!n_rows) {
+      HIPT(hipMemsetAsync(out->row_off, 0, 8, s));
+      HIPT(hipMemsetAsync(out->seq_off, 0, 8, s));
+      HIPT(hipStreamSynchronize(s));
+      return;
+    }
+    if (n_rows >= kRefuseFrom / 2) throw_error(CTOK_E_CAPACITY, "pipeline: the input reaches 4 GiB");
+    p->encodings(d_utf8, d_off, n_rows, pairs ? 2 : 1, nb, pp, s);
+    const uint64_t ni = p->n_ids, nc = p->n_cells;
+    out->n_cells = nc;
+    out->n_ids = ni;
+    if (nc > out->cells_cap || ni > out->ids_cap)
+      throw_error(CTOK_E_CAPACITY, "ctok_pipeline_encode_encodings_device: the rows need " + std::to_string(nc) + " cells, the offsets and word ids " +
+                                       std::to_string(ni) + " entries");
+    if ((nc && (!out->ids || !out->type_ids || !out->special_tokens_mask)) || (ni && (!out->offsets || !out->word_ids)))
+      throw_error(CTOK_E_ARG, "null argument");
+    if (nc) {
+      HIPT(hipMemcpyAsync(out->ids, p->r_ids, nc * 4, hipMemcpyDeviceToDevice, s));
+      HIPT(hipMemcpyAsync(out->type_ids, p->e_type.p, nc * 4, hipMemcpyDeviceToDevice, s));
+      HIPT(hipMemcpyAsync(out->special_tokens_mask, p->e_spec.p, nc * 4, hipMemcpyDeviceToDevice, s));
+    }
+    if (ni) {
+      HIPT(hipMemcpyAsync(out->word_ids, p->e_wids.p, ni * 4, hipMemcpyDeviceToDevice, s));
+      if (out->seq_ids) HIPT(hipMemcpyAsync(out->seq_ids, p->ids.p, ni * 4, hipMemcpyDeviceToDevice, s));
+      HIPT(hipMemcpyAsync(out->offsets, p->e_off.p, ni * 16, hipMemcpyDeviceToDevice, s));
+    }
+    HIPT(hipMemcpyAsync(out->row_off, p->r_row_off, (n_rows + 1) * 8, hipMemcpyDeviceToDevice, s));
+    HIPT(hipMemcpyAsync(out->seq_off, p->e_seq_off.p, (n_rows + 1) * 8, hipMemcpyDeviceToDevice, s));
+    HIPT(hipMemcpyAsync(out->n_a, p->e_na.p, n_rows * 8, hipMemcpyDeviceToDevice, s));
+    HIPT(hipStreamSynchronize(s));
+  });
+}
+
+int ctok_pipeline_encoding_stage_ms(const ctok_pipeline* p, double out[CTOK_PIPELINE_ENCODING_STAGES]) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !out) throw_error(CTOK_E_ARG, "null argument");
+    for (int i = 0; i < CTOK_PIPELINE_ENCODING_STAGES; i++) out[i] = p->enc_ms[i];
+  });
+}
+
+const char* ctok_pipeline_encoding_stage_name(uint64_t i) { return i < CTOK_PIPELINE_ENCODING_STAGES ? kEncStageNames[i] : ""; }
+
+void ctok_pipeline_encoding_limits(const ctok_pipeline* p, ctok_pipeline_encoding_limits_t* out) {
+  if (!out) return;
+  out->max_find_work = p ? p->find_cap : find_work_cap();
+  out->max_special_tokens = ctok_pe::kMaxSpecial;
+  out->max_find_compares = out->max_find_work / ctok_pe::kFindCompareShare;
+}
+
+int ctok_pipeline_encoding_stats(const ctok_pipeline* p, ctok_pipeline_encoding_info* out) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !out) throw_error(CTOK_E_ARG, "null argument");
+    *out = p->enc_info;
   });
 }
 

@@ -32,6 +32,7 @@
 
 #include "ctok.h"
 #include "ctok_normalizer.h"
+#include "ctok_postprocessor.h"
 #include "ctok_pretokenizer.h"
 
 #ifdef __cplusplus
@@ -125,6 +126,110 @@ typedef struct ctok_pipeline_info {
   uint64_t max_segment_symbols;
 } ctok_pipeline_info;
 int ctok_pipeline_stats(const ctok_pipeline* p, ctok_pipeline_info* out);
+
+/* ---- Encodings: ids with offsets, word ids and the row masks -------------------------------------------
+ *
+ * The reference's encode_to_encoding / encode_pair_to_encoding (mod.rs:340-480) before truncation and
+ * padding, for a batch.  Every text (and every pair text) is a sequence: it goes through the normaliser,
+ * the pre-tokenizer and the word BPE without the added-token loop (CTOK_PIPELINE_TOKENIZE).  Then, all on
+ * the device:
+ *   - every word, its leading 'Ġ' / '▁' chars trimmed (the whole word when nothing is left), is searched
+ *     for in the sequence's original bytes from where the previous word ended; found at pos its span is
+ *     (pos, pos + needle bytes), else (start, min(start + word bytes, text bytes)); a search that would
+ *     start inside a UTF-8 char is CTOK_E_PANIC "byte index N is not a char boundary";
+ *   - token k of a word gets (p, e), e = min(p + bytes of the id's vocab string, word end), p = the
+ *     previous e or the word's start; an id without a vocab string has no bytes, of strings that share an
+ *     id the last one counts; word_ids is the word's index in its sequence;
+ *   - row r is the ids of its text, then of its pair; pp (borrowed, may be NULL, of the same device) runs
+ *     over the merged row in the single form; type_ids are 0 for the text's ids, 1 for the pair's and 0
+ *     for what the processed row has more; special_tokens_mask is 0 for the first n cells, 1 for the
+ *     rest, and 1 wherever the processed id is a special added token's; a processed row shorter than its
+ *     ids is CTOK_E_PANIC "attempt to subtract with overflow".
+ * offsets and word_ids keep the length n of the ids before pp and are relative to their own sequence.
+ *
+ * A search scans to the text's end when the word is not there, and one wavefront walks a sequence.  With
+ * s where a word's search starts, L the text's bytes and m the needle's: work = pos - s + m on a hit,
+ * L - s on a miss; a sequence whose words' work adds up to more than ctok_pipeline_encoding_limits
+ * reports is CTOK_E_UNSUPPORTED.  The walk of such a sequence stops at the word that crosses the limit
+ * (inside it, once the work is above the limit whatever the search finds): the message holds the work
+ * counted up to there.  The work does not count what a partial match costs (a lane that finds the needle's
+ * first byte compares on): the bytes one lane compares after first bytes are bounded by max_find_compares,
+ * CTOK_E_UNSUPPORTED above it.
+ *
+ * Which error a failing call reports: CTOK_E_CAPACITY (4 GiB) and CTOK_E_UNSUPPORTED (word symbols, then
+ * find work) before any panic; of the panics that of the lowest row, its text before its pair, in a
+ * sequence the char boundary before the merge rank; the subtraction last. */
+
+typedef struct ctok_pipeline_encodings {
+  const uint32_t* ids;                 /* row_off[n_rows] processed ids */
+  const uint32_t* type_ids;
+  const uint32_t* special_tokens_mask;
+  const uint64_t* row_off;             /* n_rows + 1 */
+  const uint64_t* offsets;             /* seq_off[n_rows] (start, end) pairs */
+  const uint32_t* word_ids;            /* seq_off[n_rows] */
+  const uint32_t* seq_ids;             /* seq_off[n_rows]: the ids before pp, whose vocab strings are the tokens */
+  const uint64_t* seq_off;             /* n_rows + 1: the ids before pp */
+  const uint64_t* n_a;                 /* n_rows: of them the text's */
+  uint64_t n_rows;
+} ctok_pipeline_encodings;
+
+/* n_rows host texts and, when pair_off is not NULL, as many pair texts.  *out points into the handle and
+ * holds until its next call.  CTOK_E_ARG: a text is not UTF-8. */
+int ctok_pipeline_encode_encodings(ctok_pipeline* p, const uint8_t* utf8, const uint64_t* off, uint64_t n_rows,
+                                   const uint8_t* pair_utf8, const uint64_t* pair_off, ctok_postprocessor* pp,
+                                   ctok_pipeline_encodings* out);
+
+typedef struct ctok_pipeline_encodings_device {
+  uint32_t* ids;                 /* cells_cap each */
+  uint32_t* type_ids;
+  uint32_t* special_tokens_mask;
+  uint64_t cells_cap;
+  uint64_t* row_off;             /* n_rows + 1 */
+  uint64_t* offsets;             /* 2 * ids_cap */
+  uint32_t* word_ids;            /* ids_cap */
+  uint32_t* seq_ids;             /* ids_cap; may be NULL: not wanted */
+  uint64_t ids_cap;
+  uint64_t* seq_off;             /* n_rows + 1 */
+  uint64_t* n_a;                 /* n_rows */
+  uint64_t n_cells;              /* out: the cells and the ids before pp that the result has, also on CTOK_E_CAPACITY */
+  uint64_t n_ids;
+} ctok_pipeline_encodings_device;
+
+/* Same, with every buffer resident in the device's memory and the work ordered on `stream`.  The
+ * sequences stand in row order: with pairs != 0 sequence 2r is row r's text and 2r + 1 its pair, so d_off
+ * has n_rows * 2 + 1 entries; n_bytes is its last.  The rules of ctok_pipeline_encode_batch_device hold:
+ * the bytes are taken as they are and no byte at or past a sequence's end reaches a result; u32 arrays
+ * must be 4-byte and u64 arrays 8-byte aligned (CTOK_E_ARG before any device is used); a capacity may be
+ * exact, nothing past the counts is written; when cells_cap or ids_cap is too small the call is
+ * CTOK_E_CAPACITY with both counts returned and nothing written to any of the caller's buffers.  The call
+ * returns after the stream has finished the work. */
+int ctok_pipeline_encode_encodings_device(ctok_pipeline* p, const uint8_t* d_utf8, const uint64_t* d_off, uint64_t n_rows, int pairs,
+                                          uint64_t n_bytes, ctok_postprocessor* pp, ctok_pipeline_encodings_device* out, void* stream);
+
+/* The HIP-event time of the Encoding stages of the last such call: find, spans, rows (the post-processor
+ * inside rows); ctok_pipeline_stage_ms has the stages before them. */
+#define CTOK_PIPELINE_ENCODING_STAGES 3
+int ctok_pipeline_encoding_stage_ms(const ctok_pipeline* p, double out[CTOK_PIPELINE_ENCODING_STAGES]);
+const char* ctok_pipeline_encoding_stage_name(uint64_t i); /* "" past the end */
+
+typedef struct ctok_pipeline_encoding_limits_t {
+  uint64_t max_find_work;      /* of this handle: CTOK_PIPELINE_MAX_FIND_WORK, read at create, may lower it */
+  uint64_t max_special_tokens;
+  uint64_t max_find_compares;  /* of this handle: bytes one lane may compare after first bytes, max_find_work / 16 */
+} ctok_pipeline_encoding_limits_t;
+/* p may be NULL: the built-in limits under the current environment */
+void ctok_pipeline_encoding_limits(const ctok_pipeline* p, ctok_pipeline_encoding_limits_t* out);
+
+/* What the last Encoding call did. */
+typedef struct ctok_pipeline_encoding_info {
+  uint64_t rows;
+  uint64_t sequences;
+  uint64_t words;
+  uint64_t ids;           /* before the post-processor */
+  uint64_t cells;         /* of the processed rows */
+  uint64_t max_find_work; /* the most work of one sequence */
+} ctok_pipeline_encoding_info;
+int ctok_pipeline_encoding_stats(const ctok_pipeline* p, ctok_pipeline_encoding_info* out);
 
 #ifdef __cplusplus
 }
