@@ -275,6 +275,32 @@ class PipelineEncodingInfo(ctypes.Structure):  # ctok_pipeline_encoding_info
 CTOK_PIPELINE_ENCODING_STAGES = 3
 
 
+class PipelineWindowOpts(ctypes.Structure):  # ctok_pipeline_window_opts
+    _fields_ = [("flags", ctypes.c_uint32), ("pad_id", ctypes.c_uint32), ("max_length", ctypes.c_uint64), ("stride", ctypes.c_uint64),
+                ("want", ctypes.c_uint32)]
+
+
+class PipelineWindows(ctypes.Structure):  # ctok_pipeline_windows
+    _fields_ = [(k, ctypes.c_void_p) for k in ("ids", "attention_mask", "type_ids", "special_tokens_mask", "offsets", "word_ids",
+                                               "sequence_ids", "win_len", "win_row", "win_start", "win_off_len", "win_seq_len", "row_win")] \
+        + [(k, ctypes.c_uint64) for k in ("n_rows", "n_windows", "width")]
+
+
+class PipelineWindowsDevice(ctypes.Structure):  # ctok_pipeline_windows_device
+    _fields_ = [(k, ctypes.c_void_p) for k in ("ids", "attention_mask", "type_ids", "special_tokens_mask", "offsets", "word_ids",
+                                               "sequence_ids")] + [("cap", ctypes.c_uint64)] \
+        + [(k, ctypes.c_void_p) for k in ("win_len", "win_row", "win_start", "win_off_len", "win_seq_len")] + [("win_cap", ctypes.c_uint64)] \
+        + [("row_win", ctypes.c_void_p), ("n_windows", ctypes.c_uint64), ("width", ctypes.c_uint64)]
+
+
+class PipelineWindowInfo(ctypes.Structure):  # ctok_pipeline_window_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("rows", "windows", "width", "bytes_written")]
+
+
+CTOK_PIPELINE_WINDOW_STAGES = 2
+CTOK_PIPELINE_WIN_OFFSETS, CTOK_PIPELINE_WIN_WORD_IDS, CTOK_PIPELINE_WIN_SEQUENCE_IDS = 1, 2, 4
+
+
 class PipelineInfo(ctypes.Structure):  # ctok_pipeline_info
     _fields_ = [(k, ctypes.c_uint64) for k in ("texts", "bytes_in", "bytes_normalized", "bytes_words", "words", "segments", "symbols",
                                                "ids", "tier2_segments", "tier3_segments", "max_segment_symbols")]
@@ -467,6 +493,13 @@ SIGS = {
     "ctok_pipeline_encoding_stage_name": (ctypes.c_char_p, [_u64]),
     "ctok_pipeline_encoding_limits": (None, [_p, ctypes.POINTER(PipelineEncodingLimits)]),
     "ctok_pipeline_encoding_stats": (ctypes.c_int, [_p, ctypes.POINTER(PipelineEncodingInfo)]),
+    "ctok_pipeline_encode_windows": (ctypes.c_int, [_p, _p, _p, _u64, _p, _p, _p, ctypes.POINTER(PipelineWindowOpts),
+                                                    ctypes.POINTER(PipelineWindows)]),
+    "ctok_pipeline_encode_windows_device": (ctypes.c_int, [_p, _p, _p, _u64, _u64, _p, ctypes.POINTER(PipelineWindowOpts),
+                                                           ctypes.POINTER(PipelineWindowsDevice), _p]),
+    "ctok_pipeline_window_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double)]),
+    "ctok_pipeline_window_stage_name": (ctypes.c_char_p, [_u64]),
+    "ctok_pipeline_window_stats": (ctypes.c_int, [_p, ctypes.POINTER(PipelineWindowInfo)]),
 }
 
 for _name, (_res, _args) in SIGS.items():

@@ -588,6 +588,156 @@ class PipelineTokenizer:
         self._read_encoding_stats()
         return int(out.n_cells), int(out.n_ids)
 
+    # ------------------------------------------------------------------ padded batches and stride windows as arrays
+    # (include/ctok_pipeline.h "Padded batches and overflowing stride windows": truncation, the windows and the
+    # padding run on the device over what the Encoding call left there; csrc/pipeline_win.hip)
+
+    def _window_opts(self, what, windows, truncation, max_length, stride, add_special_tokens, pairs, padding, pad_left, pad_id, want=0):
+        ml = int(max_length) if max_length is not None else self._model_max_length
+        stride = int(stride)
+        if ml < 0 or stride < 0 or (windows and stride >= ml):
+            raise ValueError("%s: stride must be smaller than max_length (the reference loops forever)" % what)
+        f = (_n.CTOK_P_ADD_SPECIAL if add_special_tokens else 0) | (_n.CTOK_P_PAIRS if pairs else 0)
+        f |= (_n.CTOK_P_TRUNCATE | _n.CTOK_P_WINDOWS) if windows else (_n.CTOK_P_TRUNCATE if truncation else 0)
+        if padding == "longest":
+            f |= _n.CTOK_P_PAD_LONGEST
+        elif padding == "max_length":
+            f |= _n.CTOK_P_PAD_TO_MAX
+        elif padding is not None:
+            raise ValueError("%s: padding must be None, 'longest' or 'max_length'" % what)
+        if pad_left is None:
+            pad_left = self._padding_side == "left"
+        f |= (_n.CTOK_P_PAD_LEFT if pad_left else 0) | (_n.CTOK_P_PAD_ID if pad_id is not None else 0)
+        return _n.PipelineWindowOpts(f, int(pad_id or 0), ml, stride, want)
+
+    def _read_window_stats(self):
+        self._read_encoding_stats()
+        ms = (ctypes.c_double * _n.CTOK_PIPELINE_WINDOW_STAGES)()
+        info = _n.PipelineWindowInfo()
+        _n.lib.ctok_pipeline_window_stage_ms(self._h, ms)
+        _n.lib.ctok_pipeline_window_stats(self._h, ctypes.byref(info))
+        self.last_stats["windows"] = {k: int(getattr(info, k)) for k, _ in info._fields_}
+        self.last_stats["window_stages"] = [(_n.lib.ctok_pipeline_window_stage_name(i).decode(), ms[i])
+                                            for i in range(_n.CTOK_PIPELINE_WINDOW_STAGES)]
+
+    def _windows(self, what, windows, texts, pairs, truncation, max_length, stride, add_special_tokens, padding, pad_left, pad_id,
+                 return_offsets, return_word_ids, return_sequence_ids):
+        want = (_n.CTOK_PIPELINE_WIN_OFFSETS if return_offsets else 0) | (_n.CTOK_PIPELINE_WIN_WORD_IDS if return_word_ids else 0) \
+            | (_n.CTOK_PIPELINE_WIN_SEQUENCE_IDS if return_sequence_ids else 0)
+        opts = self._window_opts(what, windows, truncation, max_length, stride, add_special_tokens, pairs is not None, padding, pad_left,
+                                 pad_id, want)
+        texts = _as_str_list(texts)
+        text, off = pack_texts(texts)
+        rows = len(texts)
+        ptext = poff = None
+        if pairs is not None:
+            pairs = _as_str_list(pairs)
+            if len(pairs) != rows:
+                raise ValueError("pairs must have one entry per text")
+            ptext, poff = pack_texts(pairs)
+        out = _n.PipelineWindows()
+        pp = self._post_processor._h if self._post_processor is not None else None
+        rc = _n.lib.ctok_pipeline_encode_windows(self._h, text.ctypes.data, off.ctypes.data, rows,
+                                                 ptext.ctypes.data if ptext is not None else None,
+                                                 poff.ctypes.data if poff is not None else None, pp, ctypes.byref(opts), ctypes.byref(out))
+        if rc:
+            _raise(rc)
+        self._read_window_stats()
+        n, w = int(out.n_windows), int(out.width)
+
+        def arr(ptr, ctype, dtype, count, shape):
+            if not count:
+                return np.zeros(shape, dtype=dtype)
+            return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=(count,)).copy().reshape(shape)
+
+        def cells(ptr):
+            return arr(ptr, ctypes.c_uint32, np.uint32, n * w, (n, w))
+
+        def rec(ptr, ctype=ctypes.c_uint64, dtype=np.uint64):
+            return arr(ptr, ctype, dtype, n, (n,)).astype(np.int64)
+
+        res = {"input_ids": cells(out.ids), "attention_mask": cells(out.attention_mask), "token_type_ids": cells(out.type_ids),
+               "special_tokens_mask": cells(out.special_tokens_mask), "row_len": rec(out.win_len)}
+        if windows:
+            res["overflow_to_sample_mapping"] = rec(out.win_row, ctypes.c_uint32, np.uint32)
+            res["window_start"] = rec(out.win_start)
+            res["row_window"] = arr(out.row_win, ctypes.c_uint64, np.uint64, rows + 1, (rows + 1,)).astype(np.int64)
+        if return_offsets:
+            res["offset_mapping"] = arr(out.offsets, ctypes.c_uint64, np.uint64, 2 * n * w, (n, w, 2))
+        if return_word_ids:
+            res["word_ids"] = cells(out.word_ids)
+        if return_offsets or return_word_ids:
+            res["offsets_len"] = rec(out.win_off_len)
+        if return_sequence_ids:
+            res["sequence_ids"] = cells(out.sequence_ids)
+            res["sequence_len"] = rec(out.win_seq_len)
+        return res
+
+    def encode_padded(self, texts, pairs=None, *, add_special_tokens: bool = True, truncation: bool = False, max_length: int | None = None,
+                      padding: str | None = None, pad_left: bool | None = None, pad_id: int | None = None, return_offsets: bool = False,
+                      return_word_ids: bool = False, return_sequence_ids: bool = False) -> dict:
+        """Extension: what `__call__` computes, as [rows, width] arrays from one call on the GPU.  A row
+        longer than max_length (None: model_max_length) is cut to it when truncation is set; padding is
+        None, "longest" or "max_length", on the left with pad_left (None: padding_side == "left"); pad_id
+        None is the reference's choice ([PAD], then <pad>, then 0).  Returns uint32 input_ids,
+        attention_mask, token_type_ids, special_tokens_mask and int64 row_len [rows] (the row's Encoding
+        length); cells past it hold padding values.  On request offset_mapping uint64 [rows, width, 2],
+        word_ids and sequence_ids uint32 [rows, width] with offsets_len / sequence_len: the lists as the
+        reference leaves them -- one entry per id before the post-processor, not realigned by truncation or
+        padding -- from cell 0; past a list's end (0, 0) and 0xFFFFFFFF, which is also None inside
+        sequence_ids.  Raises PanicException where `__call__` does: a row cut between its token count and
+        its id count."""
+        return self._windows("encode_padded", False, texts, pairs, truncation, max_length, 0, add_special_tokens, padding, pad_left, pad_id,
+                             return_offsets, return_word_ids, return_sequence_ids)
+
+    def encode_windows(self, texts, pairs=None, *, max_length: int | None = None, stride: int = 0, add_special_tokens: bool = True,
+                       padding: str | None = None, pad_left: bool | None = None, pad_id: int | None = None, return_offsets: bool = False,
+                       return_word_ids: bool = False, return_sequence_ids: bool = False) -> dict:
+        """Extension: the batch cut into overflowing stride windows on the GPU
+        (Encoding::truncate_with_stride).  A row of P > max_length ids becomes 1 + ceil((P - max_length) /
+        (max_length - stride)) windows, the truncated main encoding first and its `overflowing` list after it;
+        only the main window is padded.  The keys of encode_padded, [n_windows, ...] each, and int64
+        overflow_to_sample_mapping, window_start [n_windows] and row_window [rows + 1] as
+        Tokenizer.encode_windows returns them.  stride >= max_length raises ValueError.  A row that overflows
+        with fewer tokens than ids raises PanicException, as the reference panics slicing `tokens`: after a
+        post-processor that adds ids, and with add_special_tokens=False when the row holds an added token
+        whose id is not in the vocab."""
+        return self._windows("encode_windows", True, texts, pairs, True, max_length, stride, add_special_tokens, padding, pad_left, pad_id,
+                             return_offsets, return_word_ids, return_sequence_ids)
+
+    def encode_windows_device(self, d_text: int, d_off: int, n_rows: int, n_bytes: int, *, d_ids: int, cap: int, d_win_len: int,
+                              d_win_row: int, win_cap: int, d_row_win: int, max_length: int | None = None, stride: int = 0,
+                              windows: bool = True, truncation: bool = True, d_attention: int = 0, d_type_ids: int = 0, d_special: int = 0,
+                              d_offsets: int = 0, d_word_ids: int = 0, d_sequence_ids: int = 0, d_win_start: int = 0,
+                              d_win_off_len: int = 0, d_win_seq_len: int = 0, pairs: bool = False, add_special_tokens: bool = True,
+                              padding: str | None = None, pad_left: bool | None = None, pad_id: int | None = None, stream: int = 0):
+        """Extension: encode_windows (windows=False: encode_padded) over raw device pointers (ints; e.g.
+        torch tensors' data_ptr()) of this tokenizer's device, ordered on the HIP stream `stream` (0: the
+        default stream).  With pairs the sequences are interleaved and d_off has 2 * n_rows + 1 entries.
+        d_ids and the other uint32 arrays hold cap cells, d_offsets 2 * cap uint64; d_win_len (uint64),
+        d_win_row (uint32) and the other uint64 records win_cap entries; d_row_win n_rows + 1 uint64.  0 for
+        an output that is not wanted, among all but d_ids, d_win_len, d_win_row and d_row_win.  Returns
+        (n_windows, width); raises BufferError carrying `.needed` = (n_windows, width) when a capacity is
+        too small, with d_row_win filled and nothing else written.  The bytes are taken as they are.
+        Returns after the work is done."""
+        opts = self._window_opts("encode_windows_device", windows, truncation, max_length, stride, add_special_tokens, pairs, padding,
+                                 pad_left, pad_id)
+        out = _n.PipelineWindowsDevice(d_ids or None, d_attention or None, d_type_ids or None, d_special or None, d_offsets or None,
+                                       d_word_ids or None, d_sequence_ids or None, cap, d_win_len or None, d_win_row or None,
+                                       d_win_start or None, d_win_off_len or None, d_win_seq_len or None, win_cap, d_row_win or None, 0, 0)
+        pp = self._post_processor._h if self._post_processor is not None else None
+        rc = _n.lib.ctok_pipeline_encode_windows_device(self._h, d_text or None, d_off or None, n_rows, n_bytes, pp, ctypes.byref(opts),
+                                                        ctypes.byref(out), stream or None)
+        if rc == _n.CTOK_E_CAPACITY and (out.n_windows > win_cap or out.n_windows * out.width > cap):
+            e = BufferError("encode_windows_device: %d windows of width %d are needed, the capacities are %d cells and %d windows"
+                            % (out.n_windows, out.width, cap, win_cap))
+            e.needed = (int(out.n_windows), int(out.width))
+            raise e
+        if rc:
+            _raise(rc)
+        self._read_window_stats()
+        return int(out.n_windows), int(out.width)
+
     def _pad_id_token(self):
         """mod.rs:505-510"""
         pid = self._special.get("[PAD]", self._special.get("<pad>", 0))

@@ -25,6 +25,7 @@
 #include "host_common.h"
 #include "knobs.h"
 #include "pipeline_enc_internal.h"
+#include "pipeline_win_internal.h"
 #include "train_host_common.h"
 #include "wordbpe_compile.h"
 #include "wordbpe_internal.h"
@@ -44,6 +45,8 @@ constexpr uint64_t kRefuseFrom = 0xFFFFFF00ull;  // bytes, words or texts of one
 const char* const kStageNames[CTOK_PIPELINE_STAGES] = {"normalize", "pre_tokenize", "segments", "symbols", "merges", "emit"};
 
 const char* const kEncStageNames[CTOK_PIPELINE_ENCODING_STAGES] = {"find", "spans", "rows"};
+
+const char* const kWinStageNames[CTOK_PIPELINE_WINDOW_STAGES] = {"plan", "write"};
 
 uint64_t find_work_cap() {
   uint64_t cap = ctok_pe::kMaxFindWork;
@@ -103,6 +106,15 @@ struct ctok_pipeline {
   std::vector<uint8_t> h_text;
   std::vector<uint64_t> h_off, h_row_off, h_seq_off, h_na, h_offsets;
   std::vector<uint32_t> h_out, h_type, h_spec, h_wids, h_seq_ids;
+  // padded batches and stride windows (pipeline_win.hip)
+  uint32_t default_pad_id = 0;  // the reference's choice: [PAD], then <pad>, then 0 (mod.rs:505-510)
+  hipEvent_t ev_win[2 * CTOK_PIPELINE_WINDOW_STAGES] = {};  // begin and end of plan, write
+  double win_ms[CTOK_PIPELINE_WINDOW_STAGES] = {};
+  ctok_pipeline_window_info win_info{};
+  DBuf<uint64_t> w_row_win, w_rep, w_len, w_start, w_off_len, w_seq_len, w_offsets;
+  DBuf<uint32_t> w_tokenless, w_row, w_ids, w_attn, w_type, w_spec, w_word, w_seq;
+  std::vector<uint64_t> hw_row_win, hw_len, hw_start, hw_off_len, hw_seq_len, hw_offsets;
+  std::vector<uint32_t> hw_row, hw_ids, hw_attn, hw_type, hw_spec, hw_word, hw_seq;
   // the tables
   DBuf<wordbpe::CpSlot> d_cps;
   DBuf<strmerge::PairSlot> d_pairs;
@@ -126,6 +138,10 @@ struct ctok_pipeline {
       if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_enc)
       if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_win)
+      if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_rec)
+      if (e) (void)hipEventDestroy(e);
     if (ev_merge) (void)hipEventDestroy(ev_merge);
     if (own) (void)hipStreamDestroy(own);
   }
@@ -140,6 +156,8 @@ struct ctok_pipeline {
     HIPT(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
     for (auto& e : ev) HIPT(hipEventCreate(&e));
     for (auto& e : ev_enc) HIPT(hipEventCreate(&e));
+    for (auto& e : ev_win) HIPT(hipEventCreate(&e));
+    for (auto& e : ev_rec) HIPT(hipEventCreate(&e));
     HIPT(hipEventCreate(&ev_merge));
     upload(d_len_id, len_id.data(), len_id.size(), own);
     upload(d_len_val, len_val.data(), len_val.size(), own);
@@ -530,6 +548,175 @@ struct ctok_pipeline {
     }
     if (short_row != ~0ull) throw_error(CTOK_E_PANIC, "attempt to subtract with overflow");
   }
+
+  // Host texts (and pair texts) checked and copied to in_text / in_off, the sequences in row order: 2r is
+  // row r's text, 2r + 1 its pair.  Returns the bytes.  n_rows > 0.
+  uint64_t upload_rows(const uint8_t* utf8, const uint64_t* off, uint64_t n_rows, const uint8_t* pair_utf8, const uint64_t* pair_off) {
+    if (off[0] != 0 || (pair_off && pair_off[0] != 0)) throw_error(CTOK_E_ARG, "offsets[0] must be 0");
+    for (uint64_t i = 0; i < n_rows; i++) {
+      if (off[i] > off[i + 1] || (pair_off && pair_off[i] > pair_off[i + 1])) throw_error(CTOK_E_ARG, "offsets must not decrease");
+      if (!valid_utf8(utf8, off[i], off[i + 1])) throw_error(CTOK_E_ARG, "text " + std::to_string(i) + " is not UTF-8");
+      if (pair_off && !valid_utf8(pair_utf8, pair_off[i], pair_off[i + 1]))
+        throw_error(CTOK_E_ARG, "pair text " + std::to_string(i) + " is not UTF-8");
+    }
+    const uint64_t nb = off[n_rows] + (pair_off ? pair_off[n_rows] : 0), n = n_rows * (pair_off ? 2 : 1);
+    if (nb >= kRefuseFrom || n >= kRefuseFrom) throw_error(CTOK_E_CAPACITY, "pipeline: the input reaches 4 GiB");
+    const uint8_t* text = utf8;
+    const uint64_t* toff = off;
+    if (pair_off) {
+      h_text.resize(nb);
+      h_off.resize(n + 1);
+      uint64_t at = 0;
+      for (uint64_t i = 0; i < n_rows; i++) {
+        h_off[2 * i] = at;
+        if (off[i + 1] > off[i]) std::copy(utf8 + off[i], utf8 + off[i + 1], h_text.begin() + at);
+        at += off[i + 1] - off[i];
+        h_off[2 * i + 1] = at;
+        if (pair_off[i + 1] > pair_off[i]) std::copy(pair_utf8 + pair_off[i], pair_utf8 + pair_off[i + 1], h_text.begin() + at);
+        at += pair_off[i + 1] - pair_off[i];
+      }
+      h_off[n] = at;
+      text = h_text.data();
+      toff = h_off.data();
+    }
+    HIPT(hipSetDevice(device));
+    in_text.ensure(nb + 64);
+    in_off.ensure(n + 1);
+    if (nb) HIPT(hipMemcpyAsync(in_text.p, text, nb, hipMemcpyHostToDevice, own));
+    HIPT(hipMemcpyAsync(in_off.p, toff, (n + 1) * 8, hipMemcpyHostToDevice, own));
+    return nb;
+  }
+
+  // ---- padded batches and stride windows (include/ctok_pipeline.h, "Padded batches ...") -----------------
+  ctok_pw::Win W{};
+  hipEvent_t ev_rec[2] = {};  // the records, which belong to the plan stage but run after its counts came back
+
+  static uint32_t window_mode(uint32_t flags) {
+    return (flags & CTOK_P_WINDOWS) ? pwin::kWindows : (flags & CTOK_P_TRUNCATE) ? pwin::kCut : pwin::kNone;
+  }
+
+  // The rows of a window call and their plan: everything up to n_windows and width.  The errors in order:
+  // those of the encode, then the panic of the lowest row, then the 2^32 windows.  n_rows > 0.
+  void window_plan(const uint8_t* d_text, const uint64_t* d_off, uint64_t n_rows, uint32_t per_row, uint64_t nb, ctok_postprocessor* pp,
+                   const ctok_pipeline_window_opts& o, hipStream_t s) {
+    using namespace ctok_pw;
+    for (double& t : win_ms) t = 0;
+    win_info = ctok_pipeline_window_info{};
+    win_info.rows = n_rows;
+    W = Win{};
+    if (o.flags & CTOK_P_ADD_SPECIAL) {
+      encodings(d_text, d_off, n_rows, per_row, nb, pp, s);
+      W.ids = r_ids;
+      W.type_ids = e_type.p;
+      W.special_mask = e_spec.p;
+      W.row_off = r_row_off;
+      W.offsets = e_off.p;
+      W.word_ids = e_wids.p;
+    } else {
+      // Encoding::from_ids over the id path: no post-processor, no offsets, and `tokens` without the ids that
+      // have no vocab string
+      for (double& t : enc_ms) t = 0;
+      enc_info = ctok_pipeline_encoding_info{};
+      const uint64_t n = n_rows * per_row;
+      run(d_text, d_off, n, nb, 0, s);
+      ids.ensure(n_ids + 1);
+      tok_off.ensure(n + 1);
+      emit(ids.p, tok_off.p, s);
+      e_seq_off.ensure(n_rows + 1);
+      e_na.ensure(n_rows + 1);
+      ctok_pe::Rows r{};
+      r.tok_off = tok_off.p;
+      r.per_row = per_row;
+      r.n_rows = n_rows;
+      r.seq_off = e_seq_off.p;
+      r.n_a = e_na.p;
+      HIPT(ctok_pe::launch_row_heads(r, s));
+      w_tokenless.ensure(n_rows + 1);
+      HIPT(hipMemsetAsync(w_tokenless.p, 0, n_rows * 4, s));
+      HIPT(launch_tokenless(ids.p, n_ids, e_seq_off.p, n_rows, d_len_id.p, (uint32_t)len_id.size(), w_tokenless.p, s));
+      W.ids = ids.p;
+      W.row_off = e_seq_off.p;
+      W.tokenless = w_tokenless.p;
+    }
+    W.seq_off = e_seq_off.p;
+    W.n_a = e_na.p;
+    W.n_rows = n_rows;
+    W.mode = window_mode(o.flags);
+    W.pad_left = (o.flags & CTOK_P_PAD_LEFT) ? 1 : 0;
+    W.pad_id = (o.flags & CTOK_P_PAD_ID) ? o.pad_id : default_pad_id;
+    W.m = o.max_length;
+    W.stride = W.mode == pwin::kWindows ? o.stride : 0;
+    w_row_win.ensure(n_rows + 2);
+    w_rep.ensure(kNumRep);
+    tmp64.ensure(ctok_dev::scan_tmp_elems(n_rows + 1) + 64);
+    W.row_win = w_row_win.p;
+    W.rep = (unsigned long long*)w_rep.p;
+    const uint64_t rep0[kNumRep] = {kNoRow, 0};
+    uint64_t h_rep[kNumRep] = {}, n_win = 0;
+    HIPT(hipMemcpyAsync(w_rep.p, rep0, sizeof(rep0), hipMemcpyHostToDevice, s));
+    HIPT(hipEventRecord(ev_win[0], s));
+    HIPT(launch_plan(W, s));
+    HIPT(ctok_dev::scan_u64(w_row_win.p, n_rows, tmp64.p, tmp64.cap, s));
+    HIPT(hipEventRecord(ev_win[1], s));
+    HIPT(hipMemcpyAsync(h_rep, w_rep.p, sizeof(h_rep), hipMemcpyDeviceToHost, s));
+    HIPT(hipMemcpyAsync(&n_win, w_row_win.p + n_rows, 8, hipMemcpyDeviceToHost, s));
+    HIPT(hipStreamSynchronize(s));
+    if (h_rep[kRepPanic] != kNoRow) {
+      const uint64_t r = h_rep[kRepPanic];
+      if (r >= n_rows) throw_error(CTOK_E_DEVICE, "pipeline: the panic report is out of bounds");
+      uint64_t ro[2] = {}, so[2] = {};
+      uint32_t less = 0;
+      HIPT(hipMemcpyAsync(ro, W.row_off + r, 16, hipMemcpyDeviceToHost, s));
+      HIPT(hipMemcpyAsync(so, W.seq_off + r, 16, hipMemcpyDeviceToHost, s));
+      if (W.tokenless) HIPT(hipMemcpyAsync(&less, W.tokenless + r, 4, hipMemcpyDeviceToHost, s));
+      HIPT(hipStreamSynchronize(s));
+      const uint64_t t = so[1] - so[0] - less;
+      // (the text of Encoding._slice: the package's own truncate / truncate_with_stride raise it for this row)
+      throw_error(CTOK_E_PANIC, "range end index " + std::to_string(pwin::panic_end(W.mode, ro[1] - ro[0], t, W.m, W.stride)) +
+                                    " out of range for slice of length " + std::to_string(t) + " (tokens)");
+    }
+    if (n_win < n_rows) throw_error(CTOK_E_DEVICE, "pipeline: fewer windows than rows");
+    if (n_win >> 32) throw_error(CTOK_E_ARG, "pipeline: " + std::to_string(n_win) + " windows: a call must stay below 2^32");
+    const uint64_t longest = h_rep[kRepMain];
+    W.target = (o.flags & CTOK_P_PAD_TO_MAX) ? W.m : (o.flags & CTOK_P_PAD_LONGEST) ? longest : 0;
+    W.n_windows = n_win;
+    W.width = std::max(longest, W.target);
+    win_info.windows = n_win;
+    win_info.width = W.width;
+  }
+
+  // The records and the arrays into d (capacities checked by the caller).
+  void window_write(const ctok_pipeline_windows_device& d, hipStream_t s) {
+    using namespace ctok_pw;
+    W.win_len = d.win_len;
+    W.win_row = d.win_row;
+    W.win_start = d.win_start;
+    W.win_off_len = d.win_off_len;
+    W.win_seq_len = d.win_seq_len;
+    W.out_ids = d.ids;
+    W.out_attn = d.attention_mask;
+    W.out_type = d.type_ids;
+    W.out_special = d.special_tokens_mask;
+    W.out_offsets = d.offsets;
+    W.out_word = d.word_ids;
+    W.out_seq = d.sequence_ids;
+    HIPT(hipEventRecord(ev_rec[0], s));
+    HIPT(launch_records(W, s));
+    HIPT(hipEventRecord(ev_rec[1], s));
+    HIPT(hipEventRecord(ev_win[2], s));
+    HIPT(launch_write(W, s));
+    HIPT(hipEventRecord(ev_win[3], s));
+    HIPT(hipStreamSynchronize(s));
+    float plan = 0, rec = 0, wr = 0;
+    HIPT(hipEventElapsedTime(&plan, ev_win[0], ev_win[1]));
+    HIPT(hipEventElapsedTime(&rec, ev_rec[0], ev_rec[1]));
+    HIPT(hipEventElapsedTime(&wr, ev_win[2], ev_win[3]));
+    win_ms[0] = (double)plan + rec;
+    win_ms[1] = wr;
+    const uint64_t cells = W.n_windows * W.width;
+    win_info.bytes_written = cells * 4 * (1 + (d.attention_mask != nullptr) + (d.type_ids != nullptr) + (d.special_tokens_mask != nullptr) +
+                                          (d.word_ids != nullptr) + (d.sequence_ids != nullptr)) + (d.offsets ? cells * 16 : 0);
+  }
 };
 
 namespace {
@@ -596,6 +783,8 @@ int ctok_pipeline_create(const ctok_pipeline_tables* tb, ctok_normalizer* nz, ct
       for (uint64_t i = 0; i < as.size(); i++)
         if (tb->added_flags[i] & CTOK_PIPELINE_AT_SPECIAL) special[as[i]] = tb->added_id[i];
       for (const auto& kv : special) p->special_id.push_back(kv.second);
+      for (const char* name : {"<pad>", "[PAD]"})
+        if (auto it = special.find(name); it != special.end()) p->default_pad_id = it->second;
       std::sort(p->special_id.begin(), p->special_id.end());
       p->special_id.erase(std::unique(p->special_id.begin(), p->special_id.end()), p->special_id.end());
     }
@@ -682,40 +871,8 @@ int ctok_pipeline_encode_encodings(ctok_pipeline* p, const uint8_t* utf8, const 
     for (double& t : p->stage_ms) t = 0;
     for (double& t : p->enc_ms) t = 0;
     if (!n_rows) return;
-    if (off[0] != 0 || (pair_off && pair_off[0] != 0)) throw_error(CTOK_E_ARG, "offsets[0] must be 0");
-    for (uint64_t i = 0; i < n_rows; i++) {
-      if (off[i] > off[i + 1] || (pair_off && pair_off[i] > pair_off[i + 1])) throw_error(CTOK_E_ARG, "offsets must not decrease");
-      if (!valid_utf8(utf8, off[i], off[i + 1])) throw_error(CTOK_E_ARG, "text " + std::to_string(i) + " is not UTF-8");
-      if (pair_off && !valid_utf8(pair_utf8, pair_off[i], pair_off[i + 1]))
-        throw_error(CTOK_E_ARG, "pair text " + std::to_string(i) + " is not UTF-8");
-    }
-    const uint64_t nb = off[n_rows] + (pair_off ? pair_off[n_rows] : 0), n = n_rows * per_row;
-    if (nb >= kRefuseFrom || n >= kRefuseFrom) throw_error(CTOK_E_CAPACITY, "pipeline: the input reaches 4 GiB");
-    // the sequences in row order: 2r is row r's text, 2r + 1 its pair
-    const uint8_t* text = utf8;
-    const uint64_t* toff = off;
-    if (pair_off) {
-      p->h_text.resize(nb);
-      p->h_off.resize(n + 1);
-      uint64_t at = 0;
-      for (uint64_t i = 0; i < n_rows; i++) {
-        p->h_off[2 * i] = at;
-        if (off[i + 1] > off[i]) std::copy(utf8 + off[i], utf8 + off[i + 1], p->h_text.begin() + at);
-        at += off[i + 1] - off[i];
-        p->h_off[2 * i + 1] = at;
-        if (pair_off[i + 1] > pair_off[i]) std::copy(pair_utf8 + pair_off[i], pair_utf8 + pair_off[i + 1], p->h_text.begin() + at);
-        at += pair_off[i + 1] - pair_off[i];
-      }
-      p->h_off[n] = at;
-      text = p->h_text.data();
-      toff = p->h_off.data();
-    }
-    HIPT(hipSetDevice(p->device));
+    const uint64_t nb = p->upload_rows(utf8, off, n_rows, pair_utf8, pair_off);
     hipStream_t s = p->own;
-    p->in_text.ensure(nb + 64);
-    p->in_off.ensure(n + 1);
-    if (nb) HIPT(hipMemcpyAsync(p->in_text.p, text, nb, hipMemcpyHostToDevice, s));
-    HIPT(hipMemcpyAsync(p->in_off.p, toff, (n + 1) * 8, hipMemcpyHostToDevice, s));
     p->encodings(p->in_text.p, p->in_off.p, n_rows, per_row, nb, pp, s);
     const uint64_t ni = p->n_ids, nc = p->n_cells;
     p->h_out.resize(nc), p->h_type.resize(nc), p->h_spec.resize(nc), p->h_wids.resize(ni), p->h_seq_ids.resize(ni), p->h_offsets.resize(2 * ni);
@@ -783,6 +940,134 @@ int ctok_pipeline_encode_encodings_device(ctok_pipeline* p, const uint8_t* d_utf
     HIPT(hipMemcpyAsync(out->seq_off, p->e_seq_off.p, (n_rows + 1) * 8, hipMemcpyDeviceToDevice, s));
     HIPT(hipMemcpyAsync(out->n_a, p->e_na.p, n_rows * 8, hipMemcpyDeviceToDevice, s));
     HIPT(hipStreamSynchronize(s));
+  });
+}
+
+namespace {
+
+// before any device is used
+void check_window_opts(const ctok_pipeline_window_opts* o) {
+  if (!o) throw_error(CTOK_E_ARG, "null argument");
+  if ((o->flags & CTOK_P_WINDOWS) && o->stride >= o->max_length)
+    throw_error(CTOK_E_ARG, "stride must be smaller than max_length (the reference loops forever)");
+}
+
+}  // namespace
+
+int ctok_pipeline_encode_windows(ctok_pipeline* p, const uint8_t* utf8, const uint64_t* off, uint64_t n_rows, const uint8_t* pair_utf8,
+                                 const uint64_t* pair_off, ctok_postprocessor* pp, const ctok_pipeline_window_opts* opts,
+                                 ctok_pipeline_windows* out) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !out || (n_rows && (!off || (off[n_rows] && !utf8)))) throw_error(CTOK_E_ARG, "null argument");
+    if (pair_off && n_rows && pair_off[n_rows] && !pair_utf8) throw_error(CTOK_E_ARG, "null argument");
+    check_window_opts(opts);
+    p->hw_row_win.assign(n_rows + 1, 0);
+    *out = ctok_pipeline_windows{};
+    out->row_win = p->hw_row_win.data();
+    out->n_rows = n_rows;
+    for (double& t : p->stage_ms) t = 0;
+    for (double& t : p->enc_ms) t = 0;
+    for (double& t : p->win_ms) t = 0;
+    p->win_info = ctok_pipeline_window_info{};
+    if (!n_rows) return;
+    const uint64_t nb = p->upload_rows(utf8, off, n_rows, pair_utf8, pair_off);
+    hipStream_t s = p->own;
+    p->window_plan(p->in_text.p, p->in_off.p, n_rows, pair_off ? 2 : 1, nb, pp, *opts, s);
+    const uint64_t nw = p->W.n_windows, width = p->W.width, cells = nw * width;
+    const bool offs = opts->want & CTOK_PIPELINE_WIN_OFFSETS, word = opts->want & CTOK_PIPELINE_WIN_WORD_IDS,
+               seq = opts->want & CTOK_PIPELINE_WIN_SEQUENCE_IDS;
+    ctok_pipeline_windows_device d{};
+    p->w_ids.ensure(cells + 1), p->w_attn.ensure(cells + 1), p->w_type.ensure(cells + 1), p->w_spec.ensure(cells + 1);
+    p->w_len.ensure(nw + 1), p->w_row.ensure(nw + 1), p->w_start.ensure(nw + 1), p->w_off_len.ensure(nw + 1), p->w_seq_len.ensure(nw + 1);
+    d.ids = p->w_ids.p, d.attention_mask = p->w_attn.p, d.type_ids = p->w_type.p, d.special_tokens_mask = p->w_spec.p;
+    d.win_len = p->w_len.p, d.win_row = p->w_row.p, d.win_start = p->w_start.p, d.win_off_len = p->w_off_len.p, d.win_seq_len = p->w_seq_len.p;
+    if (offs) p->w_offsets.ensure(2 * cells + 1), d.offsets = p->w_offsets.p;
+    if (word) p->w_word.ensure(cells + 1), d.word_ids = p->w_word.p;
+    if (seq) p->w_seq.ensure(cells + 1), d.sequence_ids = p->w_seq.p;
+    p->window_write(d, s);
+    const auto down32 = [&](std::vector<uint32_t>& h, const uint32_t* src, uint64_t n) {
+      h.resize(n);
+      if (n) HIPT(hipMemcpyAsync(h.data(), src, n * 4, hipMemcpyDeviceToHost, s));
+      return (const uint32_t*)h.data();
+    };
+    const auto down64 = [&](std::vector<uint64_t>& h, const uint64_t* src, uint64_t n) {
+      h.resize(n);
+      if (n) HIPT(hipMemcpyAsync(h.data(), src, n * 8, hipMemcpyDeviceToHost, s));
+      return (const uint64_t*)h.data();
+    };
+    out->ids = down32(p->hw_ids, d.ids, cells);
+    out->attention_mask = down32(p->hw_attn, d.attention_mask, cells);
+    out->type_ids = down32(p->hw_type, d.type_ids, cells);
+    out->special_tokens_mask = down32(p->hw_spec, d.special_tokens_mask, cells);
+    if (offs) out->offsets = down64(p->hw_offsets, d.offsets, 2 * cells);
+    if (word) out->word_ids = down32(p->hw_word, d.word_ids, cells);
+    if (seq) out->sequence_ids = down32(p->hw_seq, d.sequence_ids, cells);
+    out->win_len = down64(p->hw_len, d.win_len, nw);
+    out->win_row = down32(p->hw_row, d.win_row, nw);
+    out->win_start = down64(p->hw_start, d.win_start, nw);
+    out->win_off_len = down64(p->hw_off_len, d.win_off_len, nw);
+    out->win_seq_len = down64(p->hw_seq_len, d.win_seq_len, nw);
+    out->row_win = down64(p->hw_row_win, p->w_row_win.p, n_rows + 1);
+    HIPT(hipStreamSynchronize(s));
+    out->n_windows = nw;
+    out->width = width;
+  });
+}
+
+int ctok_pipeline_encode_windows_device(ctok_pipeline* p, const uint8_t* d_utf8, const uint64_t* d_off, uint64_t n_rows, uint64_t nb,
+                                        ctok_postprocessor* pp, const ctok_pipeline_window_opts* opts, ctok_pipeline_windows_device* out,
+                                        void* stream) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !out || !out->row_win || !out->win_len || !out->win_row || (n_rows && !d_off) || (nb && !d_utf8))
+      throw_error(CTOK_E_ARG, "null argument");
+    out->n_windows = out->width = 0;
+    // checked before any device is used: a refused call launches nothing and writes nothing
+    check_window_opts(opts);
+    if (((uintptr_t)out->ids | (uintptr_t)out->attention_mask | (uintptr_t)out->type_ids | (uintptr_t)out->special_tokens_mask |
+         (uintptr_t)out->word_ids | (uintptr_t)out->sequence_ids | (uintptr_t)out->win_row) & 3u)
+      throw_error(CTOK_E_ARG, "ctok_pipeline_encode_windows_device: the u32 arrays must be 4-byte aligned");
+    if (((uintptr_t)d_off | (uintptr_t)out->offsets | (uintptr_t)out->win_len | (uintptr_t)out->win_start | (uintptr_t)out->win_off_len |
+         (uintptr_t)out->win_seq_len | (uintptr_t)out->row_win) & 7u)
+      throw_error(CTOK_E_ARG, "ctok_pipeline_encode_windows_device: the u64 arrays must be 8-byte aligned");
+    HIPT(hipSetDevice(p->device));
+    hipStream_t s = (hipStream_t)stream;
+    for (double& t : p->stage_ms) t = 0;
+    for (double& t : p->enc_ms) t = 0;
+    for (double& t : p->win_ms) t = 0;
+    p->win_info = ctok_pipeline_window_info{};
+    if (!n_rows) {
+      HIPT(hipMemsetAsync(out->row_win, 0, 8, s));
+      HIPT(hipStreamSynchronize(s));
+      return;
+    }
+    if (n_rows >= kRefuseFrom / 2) throw_error(CTOK_E_CAPACITY, "pipeline: the input reaches 4 GiB");
+    p->window_plan(d_utf8, d_off, n_rows, (opts->flags & CTOK_P_PAIRS) ? 2 : 1, nb, pp, *opts, s);
+    const uint64_t nw = p->W.n_windows, width = p->W.width;
+    out->n_windows = nw;
+    out->width = width;
+    HIPT(hipMemcpyAsync(out->row_win, p->w_row_win.p, (n_rows + 1) * 8, hipMemcpyDeviceToDevice, s));
+    HIPT(hipStreamSynchronize(s));
+    if (nw > out->win_cap || nw * width > out->cap)
+      throw_error(CTOK_E_CAPACITY, "ctok_pipeline_encode_windows_device: " + std::to_string(nw) + " windows of width " + std::to_string(width) +
+                                       " are needed");
+    if (nw * width && !out->ids) throw_error(CTOK_E_ARG, "null argument");
+    p->window_write(*out, s);
+  });
+}
+
+int ctok_pipeline_window_stage_ms(const ctok_pipeline* p, double out[CTOK_PIPELINE_WINDOW_STAGES]) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !out) throw_error(CTOK_E_ARG, "null argument");
+    for (int i = 0; i < CTOK_PIPELINE_WINDOW_STAGES; i++) out[i] = p->win_ms[i];
+  });
+}
+
+const char* ctok_pipeline_window_stage_name(uint64_t i) { return i < CTOK_PIPELINE_WINDOW_STAGES ? kWinStageNames[i] : ""; }
+
+int ctok_pipeline_window_stats(const ctok_pipeline* p, ctok_pipeline_window_info* out) {
+  return ctok_host::run_guarded([&] {
+    if (!p || !out) throw_error(CTOK_E_ARG, "null argument");
+    *out = p->win_info;
   });
 }
 

@@ -231,6 +231,120 @@ typedef struct ctok_pipeline_encoding_info {
 } ctok_pipeline_encoding_info;
 int ctok_pipeline_encoding_stats(const ctok_pipeline* p, ctok_pipeline_encoding_info* out);
 
+/* ---- Padded batches and overflowing stride windows as arrays ---------------------------------------------
+ *
+ * Tokenizer.__call__'s truncation and padding (src/bindings/tokenizer.rs:33-201 over Encoding::truncate,
+ * truncate_with_stride and pad, src/encoding.rs:87-223) applied on the device to what an Encoding call
+ * leaves there: [n_windows, width] arrays, with no Encoding of lists in between.  flags are ctok.h's:
+ *   - CTOK_P_ADD_SPECIAL: the rows are those of ctok_pipeline_encode_encodings with pp.  Without it they are
+ *     Encoding::from_ids over the id path with the added-token loop (tokenizer.rs:64-97): pp is not used,
+ *     type ids and sequence ids are 0 for the text's ids and 1 for the pair's, offsets and word ids are empty.
+ *   - CTOK_P_PAIRS: the sequences are interleaved, 2r is row r's text and 2r + 1 its pair.
+ *   - CTOK_P_TRUNCATE: a row of P > m = max_length ids is cut to m (Encoding::truncate; the remainder is
+ *     not returned).  With CTOK_P_WINDOWS as well it becomes 1 + ceil((P - m) / (m - stride)) windows
+ *     (truncate_with_stride): window k holds positions [k (m - stride), min(k (m - stride) + m, P)), window 0
+ *     is the main encoding and the others are its `overflowing` list in order; stride >= m is CTOK_E_ARG
+ *     before any device is used.
+ *   - CTOK_P_PAD_LONGEST / CTOK_P_PAD_TO_MAX: window 0 of each row is padded to the longest main window of
+ *     the call / to m, in front with CTOK_P_PAD_LEFT; the pad id is the reference's ([PAD], then <pad>, then
+ *     0) unless CTOK_P_PAD_ID gives pad_id.  Overflowing windows are never padded.
+ * width = max(longest window, padding target).  Cells at or past a window's length hold padding values: the
+ * pad id, attention 0, type 0, special 1.
+ *
+ * offsets, word_ids and sequence_ids keep the reference's quirk: the lists have one entry per id before the
+ * post-processor (n, not P), and neither truncation nor padding realigns them.  Window [start, end) takes
+ * list[start .. min(end, n)) when n > start, else nothing; pad extends sequence_ids with None (in front on a
+ * left pad) and leaves the other two alone.  The arrays hold exactly those lists from cell 0: win_off_len is
+ * the length of a window's offsets and word_ids, win_seq_len that of its sequence_ids; past the length
+ * offsets are (0, 0) and the other two 0xFFFFFFFF, which also stands for None inside sequence_ids.
+ *
+ * Panics: the reference slices `tokens` -- one entry per id before the post-processor, or without
+ * CTOK_P_ADD_SPECIAL per id that has a vocab string; t of them -- at positions counted in P.  A row with
+ * P > m > t panics when it is cut, a row with P > m and P > t when it is windowed: CTOK_E_PANIC with the
+ * message of the lowest such row.  The errors of the encode come first, in their own order (above). */
+
+#define CTOK_PIPELINE_WIN_OFFSETS 1u  /* ctok_pipeline_window_opts.want: the host entry's optional arrays */
+#define CTOK_PIPELINE_WIN_WORD_IDS 2u
+#define CTOK_PIPELINE_WIN_SEQUENCE_IDS 4u
+
+typedef struct ctok_pipeline_window_opts {
+  uint32_t flags;       /* CTOK_P_* of ctok.h, as above */
+  uint32_t pad_id;      /* with CTOK_P_PAD_ID */
+  uint64_t max_length;
+  uint64_t stride;      /* with CTOK_P_WINDOWS */
+  uint32_t want;        /* CTOK_PIPELINE_WIN_*: ctok_pipeline_encode_windows only */
+} ctok_pipeline_window_opts;
+
+typedef struct ctok_pipeline_windows {
+  const uint32_t* ids;                 /* [n_windows, width] */
+  const uint32_t* attention_mask;
+  const uint32_t* type_ids;
+  const uint32_t* special_tokens_mask;
+  const uint64_t* offsets;             /* [n_windows, width, 2]; NULL unless wanted, as the next two */
+  const uint32_t* word_ids;
+  const uint32_t* sequence_ids;
+  const uint64_t* win_len;             /* [n_windows] the window's Encoding length, padding included */
+  const uint32_t* win_row;             /* its row: the overflow-to-sample mapping */
+  const uint64_t* win_start;           /* its first position in the row */
+  const uint64_t* win_off_len;         /* entries of its offsets and word_ids */
+  const uint64_t* win_seq_len;         /* entries of its sequence_ids */
+  const uint64_t* row_win;             /* [n_rows + 1]: row r's windows are row_win[r] .. row_win[r + 1] */
+  uint64_t n_rows, n_windows, width;
+} ctok_pipeline_windows;
+
+/* Host texts as ctok_pipeline_encode_encodings takes them.  *out points into the handle and holds until its
+ * next call. */
+int ctok_pipeline_encode_windows(ctok_pipeline* p, const uint8_t* utf8, const uint64_t* off, uint64_t n_rows,
+                                 const uint8_t* pair_utf8, const uint64_t* pair_off, ctok_postprocessor* pp,
+                                 const ctok_pipeline_window_opts* opts, ctok_pipeline_windows* out);
+
+typedef struct ctok_pipeline_windows_device {
+  uint32_t* ids;                 /* cap cells each */
+  uint32_t* attention_mask;      /* may be NULL: not wanted, as every pointer below but win_len, win_row, row_win */
+  uint32_t* type_ids;
+  uint32_t* special_tokens_mask;
+  uint64_t* offsets;             /* 2 * cap */
+  uint32_t* word_ids;
+  uint32_t* sequence_ids;
+  uint64_t cap;
+  uint64_t* win_len;             /* win_cap each */
+  uint32_t* win_row;
+  uint64_t* win_start;
+  uint64_t* win_off_len;
+  uint64_t* win_seq_len;
+  uint64_t win_cap;
+  uint64_t* row_win;             /* n_rows + 1 */
+  uint64_t n_windows;            /* out, also on CTOK_E_CAPACITY */
+  uint64_t width;
+} ctok_pipeline_windows_device;
+
+/* Same, with every buffer resident in the device's memory and the work ordered on `stream`; d_off and
+ * n_bytes as ctok_pipeline_encode_encodings_device takes them.  Its rules hold: the bytes are taken as they
+ * are and no byte at or past a sequence's end reaches a result; u32 arrays must be 4-byte and u64 arrays
+ * 8-byte aligned (CTOK_E_ARG before any device is used); a capacity may be exact, nothing past
+ * n_windows * width cells (twice that for offsets) and n_windows records is written; when
+ * n_windows > win_cap or n_windows * width > cap the call is CTOK_E_CAPACITY with n_windows, width and
+ * row_win filled and nothing else written.  A call of 2^32 windows or more is CTOK_E_ARG.  The call returns
+ * after the stream has finished the work. */
+int ctok_pipeline_encode_windows_device(ctok_pipeline* p, const uint8_t* d_utf8, const uint64_t* d_off, uint64_t n_rows,
+                                        uint64_t n_bytes, ctok_postprocessor* pp, const ctok_pipeline_window_opts* opts,
+                                        ctok_pipeline_windows_device* out, void* stream);
+
+/* The HIP-event time of the window stages of the last such call: plan (counts, scan, records), write;
+ * ctok_pipeline_stage_ms and ctok_pipeline_encoding_stage_ms have the stages before them. */
+#define CTOK_PIPELINE_WINDOW_STAGES 2
+int ctok_pipeline_window_stage_ms(const ctok_pipeline* p, double out[CTOK_PIPELINE_WINDOW_STAGES]);
+const char* ctok_pipeline_window_stage_name(uint64_t i); /* "" past the end */
+
+/* What the last window call did. */
+typedef struct ctok_pipeline_window_info {
+  uint64_t rows;
+  uint64_t windows;
+  uint64_t width;
+  uint64_t bytes_written; /* by the write kernel: every cell of every requested array */
+} ctok_pipeline_window_info;
+int ctok_pipeline_window_stats(const ctok_pipeline* p, ctok_pipeline_window_info* out);
+
 #ifdef __cplusplus
 }
 #endif
