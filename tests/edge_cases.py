@@ -14,6 +14,9 @@ EDGE = [
     "tab\tsep\tvalues\t", "trailing space ", " leading", "multi\n\n\nnewline", "\r\n", "a\r\nb",
     "<|endoftext|>", "x<|endoftext|>y", "a" * 33, "a" * 64, "a" * 65, "ab" * 40, "\u00e9" * 40,
     " " * 40, "!" * 50, "1" * 70, "\u4e00" * 30, "\u00e9\u0301\u0327", "\u0301abc", " \u0301",
+    # (appended: the golden file lists the documents before these)
+    # NFC expands these (4 -> 12 bytes, 3 -> 6 bytes); a 4-byte pair that composes
+    "\U0001d160", "\u0958", "\U00011099\U000110ba",
 ]
 
 
