@@ -200,6 +200,17 @@ class PretokInfo(ctypes.Structure):  # include/ctok_pretokenizer.h ctok_pretoken
     _fields_ = [(k, ctypes.c_uint64) for k in ("steps", "steps_rewriting", "bytes_in", "bytes_out", "bytes_peak", "words")]
 
 
+class PretokSplitInfo(ctypes.Structure):  # include/ctok_pretokenizer.h ctok_pretok_split_info
+    _fields_ = [("gate", ctypes.c_int32), ("n_symbols", ctypes.c_uint32), ("n_states", ctypes.c_uint32), ("n_nfa", ctypes.c_uint32),
+                ("cyclic", ctypes.c_uint32), ("table_in_lds", ctypes.c_uint32), ("longest_match", ctypes.c_uint64),
+                ("table_bytes", ctypes.c_uint64), ("reason", ctypes.c_char * 256)]
+
+
+class PretokLimits(ctypes.Structure):  # include/ctok_pretokenizer.h ctok_pretok_limits_info
+    _fields_ = [(k, ctypes.c_uint64) for k in ("max_regex_run", "max_symbols", "max_states", "max_nfa_states", "lds_table_bytes",
+                                               "scan_tile_bytes", "scan_round_bytes")]
+
+
 class DecStep(ctypes.Structure):  # include/ctok_decoder.h ctok_dec_step
     _fields_ = [("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("a", ctypes.c_void_p), ("a_len", ctypes.c_uint64),
                 ("b", ctypes.c_void_p), ("b_len", ctypes.c_uint64), ("cp", ctypes.c_uint32), ("start", ctypes.c_uint64),
@@ -451,6 +462,8 @@ SIGS = {
     "ctok_pretokenizer_create": (ctypes.c_int, [ctypes.POINTER(PretokStep), _u64, ctypes.c_int, ctypes.POINTER(_p)]),
     "ctok_pretokenizer_destroy": (None, [_p]),
     "ctok_pretok_split_class": (ctypes.c_int, [ctypes.c_char_p, _u64]),
+    "ctok_pretok_split_plan": (ctypes.c_int, [ctypes.c_char_p, _u64, ctypes.POINTER(PretokSplitInfo)]),
+    "ctok_pretok_limits": (ctypes.c_int, [ctypes.POINTER(PretokLimits)]),
     "ctok_pretokenizer_run": (ctypes.c_int, [_p, _p, _p, _u64, _p, _u64, _p, _u64, _p, _u64p, _u64p]),
     "ctok_pretokenizer_run_device": (ctypes.c_int, [_p, _p, _p, _u64, _u64, _p, _u64, _p, _u64, _p, _u64p, _u64p, _p]),
     "ctok_pretokenizer_stage_ms": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), _u64, _u64p]),

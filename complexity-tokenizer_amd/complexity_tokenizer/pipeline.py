@@ -226,13 +226,16 @@ def parse_tokenizer_json(obj) -> dict:
             "decoder": _parse_decoder(obj.get("decoder")), "post_processor": _parse_post_processor(obj.get("post_processor"), special)}
 
 
-def _build(cls, spec, device):
-    """The component object of a spec tuple (None stays None)."""
+def _build(cls, spec, device, regex_split=False):
+    """The component object of a spec tuple (None stays None).  regex_split: every `split` of a
+    PreTokenizer is made with regex=True."""
     if spec is None:
         return None
     kind = spec[0]
     if kind == "sequence":
-        return cls.sequence([_build(cls, s, device) for s in spec[1]], device=device)
+        return cls.sequence([_build(cls, s, device, regex_split) for s in spec[1]], device=device)
+    if cls is PreTokenizer and kind == "split" and regex_split:
+        return PreTokenizer.split(*spec[1:], device=device, regex=True)
     if cls is PostProcessor:
         if kind == "template":
             return PostProcessor.template(spec[1], spec[2], list(spec[3]), device=device)
@@ -310,15 +313,18 @@ class PipelineTokenizer:
     # ------------------------------------------------------------------ constructors
     @staticmethod
     def from_components(vocab, merges, normalizer=None, pre_tokenizer=None, decoder=None, post_processor=None, added_tokens=(),
-                        device=None) -> "PipelineTokenizer":
+                        device=None, regex_split=False) -> "PipelineTokenizer":
         """vocab {token: id}; merges [(left, right)] in rank order; the components are Normalizer,
         PreTokenizer, Decoder and PostProcessor objects or None (no normaliser; the whole text is one
         word; the vocab strings joined; no post-processor); added_tokens are dicts with the
-        tokenizer.json fields.  All components must be on one device (ValueError otherwise)."""
+        tokenizer.json fields.  All components must be on one device (ValueError otherwise).
+        regex_split: every `split` of the pre-tokenizer runs as PreTokenizer.split(..., regex=True)."""
         for name, c, cls in (("normalizer", normalizer, Normalizer), ("pre_tokenizer", pre_tokenizer, PreTokenizer),
                              ("decoder", decoder, Decoder), ("post_processor", post_processor, PostProcessor)):
             if c is not None and not isinstance(c, cls):
                 raise TypeError("argument '%s': '%s' object cannot be converted to '%s'" % (name, type(c).__name__, cls.__name__))
+        if regex_split and pre_tokenizer is not None:
+            pre_tokenizer = pre_tokenizer._with_regex()
         devs = {c.device for c in (normalizer, pre_tokenizer, decoder, post_processor) if c is not None}
         if device is not None:
             devs.add(int(device))
@@ -336,27 +342,29 @@ class PipelineTokenizer:
         return PipelineTokenizer(vocab, merges, normalizer, pre_tokenizer, decoder, post_processor, added, devs.pop() if devs else 0)
 
     @staticmethod
-    def from_spec(spec: dict, device: int = 0) -> "PipelineTokenizer":
+    def from_spec(spec: dict, device: int = 0, regex_split: bool = False) -> "PipelineTokenizer":
         """From what parse_tokenizer_json returns.  A `split` pattern PreTokenizer cannot run raises
-        UnsupportedConfigError, as it does there."""
+        UnsupportedConfigError, as it does there; regex_split=True makes every `split` with regex=True,
+        so that a general pattern runs where PreTokenizer's engine takes it."""
         return PipelineTokenizer.from_components(
-            spec["vocab"], spec["merges"], _build(Normalizer, spec["normalizer"], device), _build(PreTokenizer, spec["pre_tokenizer"], device),
+            spec["vocab"], spec["merges"], _build(Normalizer, spec["normalizer"], device),
+            _build(PreTokenizer, spec["pre_tokenizer"], device, regex_split),
             _build(Decoder, spec["decoder"], device), _build(PostProcessor, spec["post_processor"], device), spec["added_tokens"], device)
 
     @staticmethod
-    def from_str(json_text: str, device: int = 0) -> "PipelineTokenizer":
+    def from_str(json_text: str, device: int = 0, regex_split: bool = False) -> "PipelineTokenizer":
         """HuggingFaceTokenizer::from_str (mod.rs:168-173)."""
         try:
             obj = json.loads(json_text)
         except ValueError as e:
             raise IOError(str(e)) from None
-        return PipelineTokenizer.from_spec(parse_tokenizer_json(obj), device)
+        return PipelineTokenizer.from_spec(parse_tokenizer_json(obj), device, regex_split)
 
     @staticmethod
-    def from_file(path: str, device: int = 0) -> "PipelineTokenizer":
+    def from_file(path: str, device: int = 0, regex_split: bool = False) -> "PipelineTokenizer":
         """HuggingFaceTokenizer::from_file (mod.rs:159-166)."""
         with open(path, "r", encoding="utf-8") as f:
-            return PipelineTokenizer.from_str(f.read(), device)
+            return PipelineTokenizer.from_str(f.read(), device, regex_split)
 
     # ------------------------------------------------------------------ getters
     @property

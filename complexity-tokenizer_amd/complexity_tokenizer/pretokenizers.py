@@ -9,7 +9,11 @@ whitespace, `punctuation` and `bert` use the reference's fixed range list, `unic
 without a HIP device the constructors raise DeviceError.  A `split` pattern the Rust regex crate
 rejects is the identity, as in the reference; one it compiles runs when it is a literal or one class
 atom (`\\s \\S \\d \\D \\p{L} \\P{L} \\p{N} \\P{N}` or a bracket class of at most 32 items) with an optional
-`+`, and raises UnsupportedConfigError otherwise.  A batch whose input, or any step's output, reaches
+`+`, and raises UnsupportedConfigError otherwise, unless `split(..., regex=True)` asks for the general
+engine: then a pattern of literals, `.`, those class atoms, concatenation, `|`, groups and
+`? * + {n} {n,} {n,m}` (greedy or lazy) that cannot match the empty string runs as a DFA on the
+device, leftmost-first as the crate matches (`split_plan` says how a pattern would run, `limits` what
+bounds the engine).  A batch whose input, or any step's output, reaches
 4 GiB raises RuntimeError.
 """
 from __future__ import annotations
@@ -25,6 +29,8 @@ from .normalizers import _bool_arg, _str_arg
 _KINDS = {"whitespace": 0, "whitespace_split": 1, "byte_level": 2, "metaspace": 3, "punctuation": 4, "digits": 5, "gpt2": 6,
           "bert": 7, "char_delimiter_split": 8, "unicode_scripts": 9, "split": 10}
 _BEHAVIORS = {"Removed": 0, "Isolated": 1, "MergedWithPrevious": 2, "MergedWithNext": 3, "Contiguous": 4}
+_REGEX = 16  # CTOK_PRETOK_REGEX
+_GATES = ("rejected", "literal", "class", "unsupported", "dfa")
 
 
 def _char_arg(name, v):
@@ -116,13 +122,16 @@ class PreTokenizer:
         return PreTokenizer([(_KINDS["unicode_scripts"], 0, b"", 0)], device, "PreTokenizer.unicode_scripts()")
 
     @staticmethod
-    def split(pattern, behavior="Removed", invert=False, device=0) -> "PreTokenizer":
-        """SplitWithBehavior; a behavior string that names none means Removed (components.rs:154-160)."""
+    def split(pattern, behavior="Removed", invert=False, device=0, *, regex=False) -> "PreTokenizer":
+        """SplitWithBehavior; a behavior string that names none means Removed (components.rs:154-160).
+        regex=True (extension): a pattern that is neither a literal nor a class atom runs as a DFA
+        where the engine takes it (see `split_plan`); a literal or class atom keeps its path."""
         a = _str_arg("pattern", pattern)
         if not isinstance(behavior, str):
             raise TypeError("argument 'behavior': '%s' object cannot be converted to 'PyString'" % type(behavior).__name__)
-        f = _BEHAVIORS.get(behavior, 0) | (8 if _bool_arg("invert", invert) else 0)
-        return PreTokenizer([(_KINDS["split"], f, a, 0)], device, "PreTokenizer.split(%r, %r, %r)" % (pattern, behavior, invert))
+        f = _BEHAVIORS.get(behavior, 0) | (8 if _bool_arg("invert", invert) else 0) | (_REGEX if _bool_arg("regex", regex) else 0)
+        return PreTokenizer([(_KINDS["split"], f, a, 0)], device,
+                            "PreTokenizer.split(%r, %r, %r%s)" % (pattern, behavior, invert, ", regex=True" if regex else ""))
 
     # ---- extensions --------------------------------------------------------------------------------------
 
@@ -144,6 +153,40 @@ class PreTokenizer:
             steps += p._steps
             names.append(repr(p))
         return PreTokenizer(steps, device, "PreTokenizer.sequence([%s])" % ", ".join(names))
+
+    @staticmethod
+    def split_plan(pattern) -> dict:
+        """How `split(pattern, ..., regex=True)` would run, without a device: `gate` is "rejected" (the
+        Rust crate refuses the pattern: the identity), "literal", "class", "dfa" or "unsupported" (with
+        `reason` naming the refused construct); for "dfa" the symbols, states and NFA states of the
+        compiled pattern, whether its matches are unbounded (`cyclic`: `limits()["max_regex_run"]` then
+        applies), else the longest match in code points, and where the kernels keep the table; extension."""
+        a = _str_arg("pattern", pattern)
+        info = _n.PretokSplitInfo()
+        rc = _n.lib.ctok_pretok_split_plan(a, len(a), ctypes.byref(info))
+        if rc:
+            _raise(rc)
+        return {"gate": _GATES[info.gate], "n_symbols": info.n_symbols, "n_states": info.n_states, "n_nfa": info.n_nfa,
+                "cyclic": bool(info.cyclic), "longest_match": int(info.longest_match), "table_bytes": int(info.table_bytes),
+                "table_in_lds": bool(info.table_in_lds), "reason": info.reason.decode("utf-8", "replace")}
+
+    @staticmethod
+    def limits() -> dict:
+        """The bounds of the `regex=True` engine: `max_regex_run` (the code points a match of a pattern
+        with unbounded matches may run inside one word; CTOK_PRETOK_MAX_REGEX_RUN lowers it), the
+        compiler's caps and the kernels' table threshold and scan tiles; extension."""
+        lim = _n.PretokLimits()
+        rc = _n.lib.ctok_pretok_limits(ctypes.byref(lim))
+        if rc:
+            _raise(rc)
+        return {k: int(getattr(lim, k)) for k, _ in lim._fields_}
+
+    def _with_regex(self) -> "PreTokenizer":
+        """This pre-tokenizer with regex=True on every `split`."""
+        steps = [(k, f | _REGEX if k == _KINDS["split"] else f, a, cp) for k, f, a, cp in self._steps]
+        if steps == self._steps:
+            return self
+        return PreTokenizer(steps, self.device, self._repr + ".with_regex()")
 
     def pre_tokenize(self, text) -> list:
         """src/bindings/components.rs:170-172"""

@@ -93,4 +93,17 @@ struct WpTrainKnobs {
   bool recount = env_int("CTOK_WP_TRAIN_RECOUNT", 0) != 0;  // walk every word and count all pairs again in every round
 };
 
+// Read when a PreTokenizer handle is made and by ctok_pretok_limits (pretok_host.cpp).  A `split`
+// pattern that runs as a cyclic DFA costs a matching run of R code points about R * R / 2 steps, so a
+// start may step through at most kMaxRegexRun code points (the largest power of two
+// at which the worst case finishes within about 2 s).  The variable lowers the cap; nothing raises it.
+constexpr uint32_t kMaxRegexRun = 1u << 19;
+struct PretokKnobs {
+  uint32_t max_regex_run = [] {
+    uint64_t cap = kMaxRegexRun;
+    if (auto e = env_u64("CTOK_PRETOK_MAX_REGEX_RUN")) cap = *e < cap ? *e : cap;
+    return (uint32_t)cap;
+  }();
+};
+
 }  // namespace ctok_rt

@@ -5,7 +5,9 @@
 //   Pure splitters never touch a byte: k_pt_split maps (in_word, begin) to new bitmaps, every lane by
 //   split_bits() from the old bitmaps and a bounded neighbourhood of its byte.  What a rule needs from
 //   farther away is made by kernels before it: the literal matches (k_pt_cand marks candidates,
-//   k_pt_chain walks chains of overlapping ones), whether a word holds a match (k_pt_hit, by the
+//   k_pt_chain walks chains of overlapping ones), the matches of a general pattern (k_pt_dfa_len runs
+//   its DFA from every lead byte, k_pt_dfa_tail / k_pt_dfa_carry / k_pt_dfa_chain resolve the
+//   leftmost non-overlapping ones by a prefix max of the matches' ends), whether a word holds a match (k_pt_hit, by the
 //   word's ordinal from a scan of the begin counts), and the script carry of UnicodeScripts: "the last
 //   script value before me" is the nearest lower lane that has one (ballot, lane read), else the
 //   wavefront's running value, which starts from the carry of the wavefront tiles before
@@ -162,6 +164,98 @@ __global__ __launch_bounds__(kThreads) void k_pt_cand(Step st, Ctx x, uint8_t* c
 __global__ __launch_bounds__(kThreads) void k_pt_chain(Step st, uint64_t n, uint8_t* mark) {
   for (uint64_t p = (uint64_t)blockIdx.x * kThreads + threadIdx.x; p < n; p += (uint64_t)gridDim.x * kThreads)
     pretok::lit_chain(st, n, p, mark);
+}
+
+// ---- `split`: DFA matches --------------------------------------------------------------------------------
+
+// len[p] = the match that starts at byte p (dfa_len); *over = the lowest start that passes the cap.
+// kLds: every workgroup first copies the transition table (at most kDfaLdsBytes) into LDS.
+template <bool kLds>
+__global__ __launch_bounds__(kThreads) void k_pt_dfa_len(Tables T0, Step st, Ctx x, uint32_t* len, uint32_t* over) {
+  __shared__ uint16_t tab[kLds ? kDfaLdsBytes / 2 : 1];
+  const uint16_t* trans = st.dfa.trans;
+  if (kLds) {
+    const uint32_t ne = st.dfa.n_states * st.dfa.n_symbols;
+    for (uint32_t i = threadIdx.x; i < ne && i < kDfaLdsBytes / 2; i += kThreads) tab[i] = st.dfa.trans[i];
+    __syncthreads();
+    trans = tab;
+  }
+  const Tables T = with_nd(T0);
+  for (uint64_t p = (uint64_t)blockIdx.x * kThreads + threadIdx.x; p < x.n; p += (uint64_t)gridDim.x * kThreads) {
+    bool ov;
+    len[p] = pretok::dfa_len(T, st.dfa, trans, x, p, &ov);
+    if (ov) atomicMin(over, (uint32_t)p);
+  }
+}
+
+__device__ __forceinline__ uint32_t wave_incl_max(uint32_t v) {  // the maximum of this lane and the lanes below
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t u = (uint32_t)__shfl_up((int)v, o, 64);
+    if (lane_id() >= (uint32_t)o && u > v) v = u;
+  }
+  return v;
+}
+// where the match that starts at p ends; 0: none starts there
+__device__ __forceinline__ uint32_t match_end(const uint32_t* len, uint64_t n, uint64_t p) {
+  return p < n && len[p] ? (uint32_t)p + len[p] : 0;
+}
+
+// tmax[t] = the largest match end of wavefront tile t
+__global__ __launch_bounds__(kThreads) void k_pt_dfa_tail(const uint32_t* len, uint64_t n, uint64_t n_tiles, uint32_t* tmax) {
+  for (uint64_t t = wave_id(); t < n_tiles; t += n_waves()) {
+    uint32_t m = 0;
+    for (uint32_t k = 0; k < kWaveWords; k++) {
+      const uint32_t e = match_end(len, n, (t * kWaveWords + k) * 64 + lane_id());
+      if (e > m) m = e;
+    }
+    m = (uint32_t)__shfl((int)wave_incl_max(m), 63, 64);
+    if (lane_id() == 0) tmax[t] = m;
+  }
+}
+
+// carry[t] = the largest tmax before tile t: one workgroup, kThreads tiles a round
+__global__ __launch_bounds__(kThreads) void k_pt_dfa_carry(const uint32_t* tmax, uint64_t n_tiles, uint32_t* carry) {
+  __shared__ uint32_t wave_max[kThreads / 64];
+  __shared__ uint32_t run;
+  if (threadIdx.x == 0) run = 0;
+  __syncthreads();
+  const uint32_t w = threadIdx.x >> 6;
+  for (uint64_t base = 0; base < n_tiles; base += kThreads) {
+    const uint64_t t = base + threadIdx.x;
+    const uint32_t inc = wave_incl_max(t < n_tiles ? tmax[t] : 0);
+    const uint32_t up = (uint32_t)__shfl_up((int)inc, 1, 64);
+    if (lane_id() == 63) wave_max[w] = inc;
+    __syncthreads();
+    uint32_t pv = lane_id() ? up : 0;
+    for (uint32_t k = 0; k < w; k++) pv = wave_max[k] > pv ? wave_max[k] : pv;
+    if (run > pv) pv = run;
+    if (t < n_tiles) carry[t] = pv;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (uint32_t k = 0; k < kThreads / 64; k++)
+        if (wave_max[k] > run) run = wave_max[k];
+    __syncthreads();
+  }
+}
+
+// Every chain head walks its chain (dfa_walk).  reach(p), the largest match end before p, is the
+// tile's carry, the wavefront's running maximum and the lanes below.  (mark is zero before the
+// kernel and only the walkers write it, each inside its own chain.)
+__global__ __launch_bounds__(kThreads) void k_pt_dfa_chain(const uint32_t* len, uint64_t n, uint64_t n_tiles,
+                                                           const uint32_t* carry, uint8_t* mark) {
+  for (uint64_t t = wave_id(); t < n_tiles; t += n_waves()) {
+    uint32_t run = carry[t];
+    for (uint32_t k = 0; k < kWaveWords; k++) {
+      const uint64_t p = (t * kWaveWords + k) * 64 + lane_id();
+      if ((t * kWaveWords + k) * 64 >= n) break;  // (the same for every lane)
+      const uint32_t inc = wave_incl_max(match_end(len, n, p));
+      const uint32_t up = (uint32_t)__shfl_up((int)inc, 1, 64), top = (uint32_t)__shfl((int)inc, 63, 64);
+      uint32_t reach = lane_id() ? up : 0;
+      if (run > reach) reach = run;
+      if (p < n && len[p] && reach <= p) pretok::dfa_walk(len, n, p, mark);
+      if (top > run) run = top;
+    }
+  }
 }
 
 __global__ __launch_bounds__(kThreads) void k_pt_popc(const uint64_t* a, const uint64_t* b, uint64_t nw, uint64_t* ca,
@@ -336,6 +430,26 @@ hipError_t launch_split(const Tables& T, Step st, const Ctx& x, const Scratch& s
     PT_LAUNCHED();
     st.cand = sc.cand;
     k_pt_chain<<<grid_for(x.n), kThreads, 0, s>>>(st, x.n, sc.mark);
+    PT_LAUNCHED();
+    st.mark = sc.mark;
+  }
+  if (st.kind == pretok::K_SPLIT && st.mode == pretok::M_DFA) {
+    const uint64_t nt = wave_tiles(x.n);
+    hipError_t e = hipMemsetAsync(sc.mark, 0, x.n, s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(sc.over, 0xFF, 4, s);
+    if (e != hipSuccess) return e;
+    // (the table in LDS: a workgroup strides over many bytes, so that the copy is shared)
+    if ((uint64_t)st.dfa.n_states * st.dfa.n_symbols * 2 <= kDfaLdsBytes)
+      k_pt_dfa_len<true><<<grid_for(x.n, 2048), kThreads, 0, s>>>(T, st, x, sc.len, sc.over);
+    else
+      k_pt_dfa_len<false><<<grid_for(x.n), kThreads, 0, s>>>(T, st, x, sc.len, sc.over);
+    PT_LAUNCHED();
+    k_pt_dfa_tail<<<grid_for(nt * 64), kThreads, 0, s>>>(sc.len, x.n, nt, sc.tmax);
+    PT_LAUNCHED();
+    k_pt_dfa_carry<<<1, kThreads, 0, s>>>(sc.tmax, nt, sc.tcarry);
+    PT_LAUNCHED();
+    k_pt_dfa_chain<<<grid_for(nt * 64), kThreads, 0, s>>>(sc.len, x.n, nt, sc.tcarry, sc.mark);
     PT_LAUNCHED();
     st.mark = sc.mark;
   }

@@ -11,7 +11,8 @@
 //                    from the text and the old bitmaps.  A rule reads the code point at p, its
 //                    predecessor in the same word and a bounded neighbourhood (GPT2_PATTERN: three
 //                    bytes either way, as csrc/seg_lane.h words it).  Three things come from outside:
-//                    the literal matches of `split` (lit_cand / lit_chain mark them), whether a word
+//                    the literal and DFA matches of `split` (lit_cand / lit_chain and dfa_len /
+//                    dfa_walk mark them), whether a word
 //                    holds a match at all (Removed without invert keeps a word that holds none), and
 //                    the script carry of UnicodeScripts (script_val: the caller finds the nearest
 //                    value before p).
@@ -37,14 +38,17 @@ enum Kind : uint32_t {  // include/ctok_pretokenizer.h
   K_SCRIPTS, K_SPLIT
 };
 enum Behavior : uint32_t { B_REMOVED, B_ISOLATED, B_MERGED_PREV, B_MERGED_NEXT, B_CONTIGUOUS };
-enum Mode : uint32_t { M_IDENTITY, M_LITERAL, M_CLASS };  // how a `split` pattern runs
-constexpr uint32_t kInvert = 8;                           // flag bit of `split`
+enum Mode : uint32_t { M_IDENTITY, M_LITERAL, M_CLASS, M_DFA };  // how a `split` pattern runs
+constexpr uint32_t kInvert = 8;                                  // flag bit of `split`
+constexpr uint32_t kRegex = 16;                                  // flag bit of `split`: a general pattern may run as a DFA
 // class items: type, lo, hi (three u32 each)
 enum Item : uint32_t { I_RANGE, I_SPACE, I_DIGIT, I_LETTER, I_NUMBER, I_NEG = 0x100 };
 // script values of script_val: 0 = nothing to say (Common, or no lead byte), kReset = a word ends or starts
 constexpr uint32_t kCommon = 0, kUnknown = 11, kReset = 15;
-// literal marks
+// marks of the applied matches (literal and DFA)
 constexpr uint8_t kInMatch = 1, kMatchStart = 2;
+// a DFA transition entry (regex_dfa.h): kDfaDead, or the next state with kDfaAccept when it holds a match
+constexpr uint16_t kDfaDead = 0xFFFF, kDfaAccept = 0x8000, kDfaState = 0x0FFF;
 constexpr uint32_t kMaxUnit = 8;  // output bytes of one input byte under a rewriter: Metaspace, two replacements
 
 struct Tables {
@@ -53,6 +57,16 @@ struct Tables {
   const uint32_t* nd_lo;  // gen/pretok_data.h
   const uint32_t* nd_hi;
   uint32_t n_nd;
+};
+
+// A general `split` pattern as regex_dfa.h compiled it.
+struct Dfa {
+  const uint16_t* trans;   // [state][symbol]
+  const uint8_t* ascii;    // symbol of a code point below 0x80
+  const uint32_t* bounds;  // interval starts, bounds[0] = 0
+  const uint8_t* symmap;   // [interval][cls * 2 + nd]
+  uint32_t n_bounds, n_symbols, n_states, raw_sym, use, start;
+  uint32_t cap;            // code points a start may step through (the work bound of a cyclic DFA)
 };
 
 struct Step {
@@ -64,7 +78,8 @@ struct Step {
   uint32_t cp_len;                    // Metaspace: the replacement's UTF-8
   uint8_t cp_u8[4];
   const uint8_t* cand;                // literal: cand[p] = 1: the literal matches at p, inside p's word
-  const uint8_t* mark;                // literal: kInMatch / kMatchStart of the applied matches
+  const uint8_t* mark;                // literal, DFA: kInMatch / kMatchStart of the applied matches
+  Dfa dfa;                            // split, M_DFA
   const uint64_t* wpos;               // Removed: words that begin before bitmap word j
   const uint8_t* whit;                // Removed: whit[w] = 1: word w holds a match
 };
@@ -256,11 +271,74 @@ NZ_HD void lit_chain(const Step& st, uint64_t n, uint64_t p, uint8_t* mark) {
   }
 }
 
+// ---- DFA matches of `split` ---------------------------------------------------------------------------
+
+NZ_HD uint32_t dfa_sym(const Tables& T, const Dfa& d, uint32_t c) {
+  if (c == kRaw || c >= 0x110000u) return d.raw_sym;
+  if (c < 0x80u) return d.ascii[c];
+  uint32_t lo = 0, hi = d.n_bounds;  // the first interval that starts past c
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (d.bounds[mid] <= c) lo = mid + 1;
+    else hi = mid;
+  }
+  uint32_t key = 0;
+  if (d.use & 1u) {
+    const uint32_t cl = cls(T, c);
+    key = cl * 2 + ((d.use & 2u) && cl == 2 && is_nd(T, c) ? 1 : 0);
+  }
+  return d.symmap[(lo - 1) * 8 + key];
+}
+// The leftmost-first match that starts at byte p, in bytes; 0: none, or p is no lead byte inside a word.
+// The DFA steps code point by code point to the dead state or the word's end, and the last accepting
+// state it saw ends the match.  *over: the run would pass d.cap code points (then 0 is returned).
+// `trans` is d.trans or a copy of it.
+NZ_HD uint32_t dfa_len(const Tables& T, const Dfa& d, const uint16_t* trans, const Ctx& x, uint64_t p, bool* over) {
+  *over = false;
+  if (!in_word(x, p) || unit_lead(x, p) != p) return 0;
+  uint32_t state = d.start, best = 0, steps = 0;
+  for (uint64_t q = p; q < x.n && in_word(x, q) && (q == p || !bit(x.beg, q));) {
+    if (steps == d.cap) {
+      *over = true;
+      return 0;
+    }
+    uint32_t l;
+    const uint32_t c = cp_at(x, q, &l);
+    const uint16_t e = trans[state * d.n_symbols + dfa_sym(T, d, c)];
+    if (e == kDfaDead) break;
+    state = e & kDfaState;
+    q += l;
+    steps++;
+    if (e & kDfaAccept) best = (uint32_t)(q - p);
+  }
+  return best;
+}
+// Matches are taken left to right and do not overlap.  reach(q) is the largest p + len[p] over the
+// candidates p < q; a candidate q with reach(q) <= q is a chain head, a match whatever lies before
+// it.  The head's thread walks its chain: it takes the match, goes on to the first candidate at or
+// after the match's end and stops where the next head would stand, that is where no candidate since
+// the head reaches.  It writes only inside [p, the chain's reach), which no other chain shares.
+NZ_HD void dfa_walk(const uint32_t* len, uint64_t n, uint64_t p, uint8_t* mark) {
+  uint64_t cur = p, end = p + len[p], reach = end;
+  for (uint64_t r = p;; r++) {
+    if (r < end) mark[r] = r == cur ? (kInMatch | kMatchStart) : kInMatch;
+    if (r + 1 >= n || r + 1 >= reach) break;
+    const uint64_t l = len[r + 1];
+    if (!l) continue;
+    if (r + 1 >= end) {
+      cur = r + 1;
+      end = cur + l;
+    }
+    if (r + 1 + l > reach) reach = r + 1 + l;
+  }
+}
+
 // ---- the pure splitters --------------------------------------------------------------------------------
 
+NZ_HD bool by_marks(const Step& st) { return st.mode == M_LITERAL || st.mode == M_DFA; }
 // the unit at a lead byte lies in a match of the `split` step
 NZ_HD bool split_in(const Tables& T, const Step& st, const Ctx& x, uint64_t lead, uint32_t c) {
-  return st.mode == M_LITERAL ? (st.mark[lead] & kInMatch) != 0 : class_match(T, st, c);
+  return by_marks(st) ? (st.mark[lead] & kInMatch) != 0 : class_match(T, st, c);
 }
 
 // the word ordinal of byte p (inside a word; 0 for bytes before the first begin, which a batch
@@ -335,7 +413,7 @@ NZ_HD void split_bits(const Tables& T, const Step& st, const Ctx& x, uint64_t p,
     default: {  // K_SPLIT
       const uint32_t b = st.flags & 7u;
       const bool m = split_in(T, st, x, lead, c), pm = prev && split_in(T, st, x, plead, pc);
-      const bool s = st.mode == M_LITERAL ? (st.mark[lead] & kMatchStart) != 0 : m && (!st.plus || !pm);
+      const bool s = by_marks(st) ? (st.mark[lead] & kMatchStart) != 0 : m && (!st.plus || !pm);
       if (b == B_REMOVED && (st.flags & kInvert)) {
         drop = m;
         pdrop = pm;

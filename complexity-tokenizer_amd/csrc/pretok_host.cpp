@@ -11,6 +11,8 @@
 // replacement as a text, and the gather places them.  There is no CPU path.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -20,6 +22,7 @@
 #include "ctok_internal.h"  // ctok_dev::scan_u64, scan_tmp_elems
 #include "gen/unicode_data.h"
 #include "host_common.h"
+#include "knobs.h"
 #include "pretok_internal.h"
 #include "pretok_prog.h"
 #include "rust_regex.h"
@@ -67,12 +70,16 @@ struct ctok_pretokenizer {
   // the steps' class items and literals on the device: step i's at at[i]
   std::string blob;
   std::vector<uint64_t> at;
+  std::vector<pretok::StepBlob> parts;
+  // the code points one start of a cyclic DFA may step through (read once, when the handle is made)
+  uint32_t max_run = ctok_rt::PretokKnobs().max_regex_run;
   DBuf<uint8_t> d_blob, d_cls1, d_cls2;
   bool ready = false;
   hipStream_t own = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   DBuf<uint64_t> inw[2], beg[2], off[2], len, tmp, wpos, cb, cw, ex, in_off, o_woff, o_tw, d_ew_off;
   DBuf<uint8_t> buf[2], flags, tail, carry, cand, mark, whit, in_text, o_words, d_ew_bytes;
+  DBuf<uint32_t> mlen, tmax, tcarry, over;
   // the words of an empty text
   pretok::EmptyFate fate = pretok::E_NOTHING;
   size_t fate_at = 0;
@@ -96,14 +103,14 @@ struct ctok_pretokenizer {
     HostStep h;
     bool unsupported = false;
     const bool rejected = s.kind == CTOK_PRETOK_SPLIT && !ctok_rt::rust_regex_rejects(a).empty();
-    const char* err = pretok::make_step(s.kind, s.flags, a, s.cp, rejected, &h, &unsupported);
-    if (err)
+    const std::string err = pretok::make_step(s.kind, s.flags, a, s.cp, rejected, &h, &unsupported);
+    if (!err.empty())
       throw_error(unsupported ? CTOK_E_UNSUPPORTED : CTOK_E_ARG,
                   std::string("pre-tokenizer step ") + std::to_string(prog.size()) + (unsupported ? ": split pattern " + a : "") + ": " + err);
     while (blob.size() % 4) blob.push_back('\0');
     at.push_back(blob.size());
-    blob.append((const char*)h.items.data(), h.items.size() * 4);
-    blob += h.lit;
+    parts.push_back(pretok::step_blob(h));
+    blob += parts.back().bytes;
     prog.push_back(h);
   }
 
@@ -124,23 +131,7 @@ struct ctok_pretokenizer {
 
   pretok::Tables tables() const { return pretok::Tables{d_cls1.p, d_cls2.p, nullptr, nullptr, 0}; }  // (\d: the kernels' own)
 
-  pretok::Step step_of(size_t i) const {
-    const HostStep& h = prog[i];
-    pretok::Step st{};
-    st.kind = h.kind;
-    st.flags = h.flags;
-    st.cp = h.cp;
-    st.mode = h.mode;
-    st.plus = h.plus;
-    st.neg = h.neg;
-    st.n_items = (uint32_t)(h.items.size() / 3);
-    st.items = (const uint32_t*)(d_blob.p + at[i]);
-    st.lit = d_blob.p + at[i] + h.items.size() * 4;
-    st.lit_len = (uint32_t)h.lit.size();
-    st.cp_len = (uint32_t)h.cp_u8.size();
-    memcpy(st.cp_u8, h.cp_u8.data(), h.cp_u8.size());
-    return st;
-  }
+  pretok::Step step_of(size_t i) const { return pretok::step_view(prog[i], parts[i], d_blob.p + at[i], max_run); }
 
   void ensure_bits(int w, uint64_t n) {
     inw[w].ensure(words64(n) + 1);
@@ -169,6 +160,19 @@ struct ctok_pretokenizer {
         sc.cand = cand.p;
         sc.mark = mark.p;
       }
+      const bool dfa = st.kind == pretok::K_SPLIT && st.mode == pretok::M_DFA && cur.n;
+      if (dfa) {
+        mark.ensure(cur.n + 1);
+        mlen.ensure(cur.n + 1);
+        tmax.ensure(ctok_pt::wave_tiles(cur.n) + 1);
+        tcarry.ensure(ctok_pt::wave_tiles(cur.n) + 1);
+        over.ensure(1);
+        sc.mark = mark.p;
+        sc.len = mlen.p;
+        sc.tmax = tmax.p;
+        sc.tcarry = tcarry.p;
+        sc.over = over.p;
+      }
       if (st.kind == pretok::K_SPLIT && st.mode != pretok::M_IDENTITY && (st.flags & 15u) == pretok::B_REMOVED && cur.n) {
         wpos.ensure(nw + 1);
         tmp.ensure(ctok_dev::scan_tmp_elems(nw + 1) + 64);
@@ -180,6 +184,7 @@ struct ctok_pretokenizer {
         sc.whit = whit.p;
       }
       HIPT(ctok_pt::launch_split(T, st, x, sc, Bits{inw[nb].p, beg[nb].p}, s));
+      if (dfa) refuse_long_run(i, cur, n_docs, s);
       return State{cur.text, cur.off, cur.n, nb};
     }
     info.steps_rewriting++;
@@ -208,6 +213,22 @@ struct ctok_pretokenizer {
     return State{buf[w].p, off[w].p, total, nb};
   }
 
+  // A start of step i's DFA passed the cap: CTOK_E_UNSUPPORTED naming the lowest-numbered such text.
+  // (The step's bitmaps are scratch: nothing has reached the caller's buffers.)
+  void refuse_long_run(size_t i, const State& cur, uint64_t n_docs, hipStream_t s) {
+    uint32_t at_byte = 0;
+    HIPT(hipMemcpyAsync(&at_byte, over.p, 4, hipMemcpyDeviceToHost, s));
+    HIPT(hipStreamSynchronize(s));
+    if (at_byte == 0xFFFFFFFFu) return;
+    std::vector<uint64_t> h_off(n_docs + 1);
+    HIPT(hipMemcpyAsync(h_off.data(), cur.off, (n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPT(hipStreamSynchronize(s));
+    const uint64_t text = (uint64_t)(std::upper_bound(h_off.begin(), h_off.end(), (uint64_t)at_byte) - h_off.begin()) - 1;
+    throw_error(CTOK_E_UNSUPPORTED, "pre-tokenizer step " + std::to_string(i) + ": text " + std::to_string(text) +
+                                        " holds a word in which a match of the split pattern may run past " +
+                                        std::to_string(max_run) + " code points, the cap of a pattern whose matches are unbounded");
+  }
+
   // the words an empty text owns (once; a run of another handle on this handle's device)
   void prepare_fate() {
     if (fate_ready) return;
@@ -218,7 +239,8 @@ struct ctok_pretokenizer {
       sub.device = device;
       for (size_t i = fate_at; i < prog.size(); i++) {
         sub.at.push_back(sub.blob.size());
-        sub.blob.append(blob, at[i], (i + 1 < at.size() ? at[i + 1] : blob.size()) - at[i]);
+        sub.parts.push_back(parts[i]);
+        sub.blob += parts[i].bytes;
         sub.prog.push_back(prog[i]);
       }
       sub.prog[0].flags &= ~1u;  // (Metaspace with a prefix over "" is Metaspace without one over the replacement)
@@ -391,6 +413,46 @@ int ctok_pretok_split_class(const uint8_t* pattern, uint64_t len) {
   const std::string p(pattern ? (const char*)pattern : "", pattern ? len : 0);
   if (!ctok_rt::rust_regex_rejects(p).empty()) return pretok::PC_REJECTED;
   return (int)pretok::classify_split(p, nullptr);
+}
+
+int ctok_pretok_split_plan(const uint8_t* pattern, uint64_t len, ctok_pretok_split_info* out) {
+  return ctok_host::run_guarded([&] {
+    if (!out || (len && !pattern)) throw_error(CTOK_E_ARG, "null argument");
+    *out = ctok_pretok_split_info{};
+    const std::string p(pattern ? (const char*)pattern : "", pattern ? len : 0);
+    std::string why = ctok_rt::rust_regex_rejects(p);
+    HostStep h;
+    if (!why.empty()) {
+      out->gate = pretok::PC_REJECTED;
+      why = "the Rust regex crate rejects the pattern: " + why;
+    } else {
+      out->gate = (int32_t)pretok::plan_split(p, &h, &why);
+    }
+    if (out->gate == pretok::PC_DFA) {
+      out->n_symbols = h.dfa.n_symbols;
+      out->n_states = h.dfa.n_states;
+      out->n_nfa = h.dfa.n_nfa;
+      out->cyclic = h.dfa.cyclic ? 1 : 0;
+      out->longest_match = h.dfa.longest;
+      out->table_bytes = (uint64_t)h.dfa.trans.size() * 2;
+      out->table_in_lds = out->table_bytes <= ctok_pt::kDfaLdsBytes ? 1 : 0;
+    }
+    snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
+  });
+}
+
+int ctok_pretok_limits(ctok_pretok_limits_info* out) {
+  return ctok_host::run_guarded([&] {
+    if (!out) throw_error(CTOK_E_ARG, "null argument");
+    *out = ctok_pretok_limits_info{};
+    out->max_regex_run = ctok_rt::PretokKnobs().max_regex_run;
+    out->max_symbols = regex_dfa::kMaxSymbols;
+    out->max_states = regex_dfa::kMaxStates;
+    out->max_nfa_states = regex_dfa::kMaxNfa;
+    out->lds_table_bytes = ctok_pt::kDfaLdsBytes;
+    out->scan_tile_bytes = ctok_pt::kWaveTile;
+    out->scan_round_bytes = (uint64_t)ctok_pt::kWaveTile * ctok_pt::kThreads;
+  });
 }
 
 int ctok_pretokenizer_run(ctok_pretokenizer* pt, const uint8_t* utf8, const uint64_t* off, uint64_t n_texts, uint8_t* words,

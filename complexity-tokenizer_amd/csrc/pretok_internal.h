@@ -26,7 +26,9 @@ inline uint64_t wave_tiles(uint64_t n) { return (n + kWaveTile - 1) / kWaveTile;
 // every text one word: in_word everywhere, begin at the first byte of every non-empty text
 hipError_t launch_init(uint64_t n, const uint64_t* doc_off, uint64_t n_docs, Bits out, hipStream_t s);
 // A pure splitter: out = the step over x.  UnicodeScripts: tail and carry have wave_tiles(n) entries.
-// A literal `split`: cand and mark have n bytes.  Removed without invert: wpos has words64(n) + 1
+// A literal `split`: cand and mark have n bytes.  A DFA `split` (M_DFA): mark has n bytes, len n entries,
+// tmax and tcarry wave_tiles(n) entries (the prefix max of the matches' ends, tile by tile), *over is
+// 0xFFFFFFFF and receives the lowest start whose run passes the step's cap.  Removed without invert: wpos has words64(n) + 1
 // entries, tmp is scan_u64's, whit has room for every word (one per begin bit) + 1.
 struct Scratch {
   uint8_t* tail;
@@ -37,7 +39,14 @@ struct Scratch {
   uint64_t* tmp;
   uint64_t tmp_cap;
   uint8_t* whit;
+  uint32_t* len;
+  uint32_t* tmax;
+  uint32_t* tcarry;
+  uint32_t* over;
 };
+// A DFA's transition table is copied into LDS when it has at most this many bytes: five workgroups of
+// kThreads then still fit the 160 KiB of a CU.  A larger table is read from global memory.
+constexpr uint32_t kDfaLdsBytes = 32u << 10;
 hipError_t launch_split(const pretok::Tables& T, pretok::Step st, const pretok::Ctx& x, const Scratch& sc, Bits out,
                         hipStream_t s);
 // words that begin in the batch (a host value; the stream is waited for)

@@ -9,6 +9,7 @@
 
 #include "../../include/ctok_pretokenizer.h"
 #include "pretok_hd.h"
+#include "regex_dfa.h"
 
 namespace pretok {
 
@@ -17,6 +18,7 @@ struct HostStep {
   uint32_t mode = M_IDENTITY, plus = 0, neg = 0;
   std::vector<uint32_t> items;  // M_CLASS: type, lo, hi
   std::string lit;              // M_LITERAL
+  regex_dfa::Dfa dfa;           // M_DFA
   std::string cp_u8;            // Metaspace: the replacement
 };
 
@@ -27,7 +29,7 @@ inline const char* kind_name(uint32_t kind) {
 }
 inline bool rewrites(uint32_t kind) { return kind == K_BYTE_LEVEL || kind == K_METASPACE; }
 
-enum PatternClass { PC_REJECTED = 0, PC_LITERAL = 1, PC_CLASS = 2, PC_UNSUPPORTED = 3 };
+enum PatternClass { PC_REJECTED = 0, PC_LITERAL = 1, PC_CLASS = 2, PC_UNSUPPORTED = 3, PC_DFA = 4 };
 
 // Gates 2 and 3 of a pattern the Rust crate compiles: a literal, or one class atom with an optional
 // '+'.  Everything else is PC_UNSUPPORTED: never split differently in silence.
@@ -164,10 +166,84 @@ inline PatternClass classify_split(const std::string& p, HostStep* out) {
   return PC_CLASS;
 }
 
+// Gate 4, for a step that carries kRegex: a pattern no earlier gate takes, compiled to a DFA
+// (regex_dfa.h).  PC_DFA, or PC_UNSUPPORTED with *why naming the construct that is refused.
+inline PatternClass plan_split(const std::string& p, HostStep* out, std::string* why) {
+  const PatternClass c = classify_split(p, out);
+  if (c != PC_UNSUPPORTED) return c;
+  regex_dfa::Dfa d;
+  *why = regex_dfa::compile(p, &d);
+  if (!why->empty()) return PC_UNSUPPORTED;
+  if (out) {
+    out->mode = M_DFA;
+    out->dfa = d;
+  }
+  return PC_DFA;
+}
+
+// The step's class items, literal and DFA tables as one block the rules read (4-byte aligned), and
+// where the literal and the DFA's four arrays start in it.
+struct StepBlob {
+  std::string bytes;
+  size_t lit = 0, trans = 0, ascii = 0, bounds = 0, symmap = 0;
+};
+inline StepBlob step_blob(const HostStep& h) {
+  StepBlob b;
+  auto pad = [&] {
+    while (b.bytes.size() % 4) b.bytes.push_back('\0');
+  };
+  b.bytes.append((const char*)h.items.data(), h.items.size() * 4);
+  b.lit = b.bytes.size();
+  b.bytes += h.lit;
+  if (h.mode == M_DFA) {
+    pad();
+    b.bounds = b.bytes.size();
+    b.bytes.append((const char*)h.dfa.bounds.data(), h.dfa.bounds.size() * 4);
+    b.trans = b.bytes.size();
+    b.bytes.append((const char*)h.dfa.trans.data(), h.dfa.trans.size() * 2);
+    b.ascii = b.bytes.size();
+    b.bytes.append((const char*)h.dfa.ascii, 128);
+    b.symmap = b.bytes.size();
+    b.bytes.append((const char*)h.dfa.symmap.data(), h.dfa.symmap.size());
+  }
+  pad();
+  return b;
+}
+// the Step the rules take, its pointers into the block at `base`; cap: the work bound of a cyclic DFA
+inline Step step_view(const HostStep& h, const StepBlob& b, const uint8_t* base, uint32_t cap) {
+  Step st{};
+  st.kind = h.kind;
+  st.flags = h.flags;
+  st.cp = h.cp;
+  st.mode = h.mode;
+  st.plus = h.plus;
+  st.neg = h.neg;
+  st.n_items = (uint32_t)(h.items.size() / 3);
+  st.items = (const uint32_t*)base;
+  st.lit = base + b.lit;
+  st.lit_len = (uint32_t)h.lit.size();
+  st.cp_len = (uint32_t)h.cp_u8.size();
+  memcpy(st.cp_u8, h.cp_u8.data(), h.cp_u8.size());
+  if (h.mode == M_DFA) {
+    st.dfa.trans = (const uint16_t*)(base + b.trans);
+    st.dfa.ascii = base + b.ascii;
+    st.dfa.bounds = (const uint32_t*)(base + b.bounds);
+    st.dfa.symmap = base + b.symmap;
+    st.dfa.n_bounds = (uint32_t)h.dfa.bounds.size();
+    st.dfa.n_symbols = h.dfa.n_symbols;
+    st.dfa.n_states = h.dfa.n_states;
+    st.dfa.raw_sym = h.dfa.raw_sym;
+    st.dfa.use = h.dfa.use;
+    st.dfa.start = h.dfa.start;
+    st.dfa.cap = h.dfa.cyclic ? cap : 0xFFFFFFFFu;
+  }
+  return st;
+}
+
 // One step of the ABI as a HostStep (a split's pattern already classified by the caller's gate 1:
-// rejected = the Rust crate refuses it, the step is the identity).  An error text, or null;
+// rejected = the Rust crate refuses it, the step is the identity).  An error text, or "";
 // *unsupported is set when the text names a pattern no gate takes.
-inline const char* make_step(uint32_t kind, uint32_t flags, const std::string& a, uint32_t cp, bool rejected, HostStep* out,
+inline std::string make_step(uint32_t kind, uint32_t flags, const std::string& a, uint32_t cp, bool rejected, HostStep* out,
                              bool* unsupported) {
   *unsupported = false;
   if (kind > K_SPLIT) return "unknown kind";
@@ -184,12 +260,20 @@ inline const char* make_step(uint32_t kind, uint32_t flags, const std::string& a
     if (a.size() >= (1ull << 32)) return "the pattern reaches 4 GiB";
     if (rejected) {
       out->mode = M_IDENTITY;
-    } else if (classify_split(a, out) == PC_UNSUPPORTED) {
-      *unsupported = true;
-      return "the pattern is neither a literal nor one class atom with an optional '+'";
+    } else if (!(flags & kRegex)) {
+      if (classify_split(a, out) == PC_UNSUPPORTED) {
+        *unsupported = true;
+        return "the pattern is neither a literal nor one class atom with an optional '+'";
+      }
+    } else {
+      std::string why;
+      if (plan_split(a, out, &why) == PC_UNSUPPORTED) {
+        *unsupported = true;
+        return "the regex engine refuses " + why;
+      }
     }
   }
-  return nullptr;
+  return "";
 }
 
 // What becomes of the empty word (an empty text) under steps [from, ..): `split` passes it on, Metaspace

@@ -2,7 +2,8 @@
 // tests/test_pretok_cpu.py, which compares its output with a restatement in plain Python.
 // Build: g++ -O1 -std=c++17 -fsanitize=address,undefined pretok_check.cpp -o pretok_check
 // stdin:  u64 n_steps, per step u32 kind, u32 flags, u32 cp, u64 a_len, a (the steps of
-//         include/ctok_pretokenizer.h; a pattern the Rust crate rejects comes with kind | 0x100);
+//         include/ctok_pretokenizer.h, a split's flags with CTOK_PRETOK_REGEX or without; a pattern the
+//         Rust crate rejects comes with kind | 0x100);
 //         then u64 n, u64 off[n + 1] and off[n] bytes: n texts
 // stdout: u64 n_words, u64 n_bytes, u64 text_word[n + 1], u64 word_off[n_words + 1], the bytes
 // pretok_check --classify PATTERN prints 1 (literal), 2 (class atom) or 3 (unsupported).
@@ -18,6 +19,7 @@
 
 #include "../csrc/gen/pretok_data.h"
 #include "../csrc/gen/unicode_data.h"
+#include "../csrc/regex_dfa.cpp"
 #include "../csrc/pretok_hd.h"
 #include "../csrc/pretok_prog.h"
 
@@ -38,25 +40,14 @@ struct Words {
   std::vector<uint8_t> bytes;
 };
 
-static Step dev_step(const HostStep& h) {
-  Step st{};
-  st.kind = h.kind;
-  st.flags = h.flags;
-  st.cp = h.cp;
-  st.mode = h.mode;
-  st.plus = h.plus;
-  st.neg = h.neg;
-  st.n_items = (uint32_t)(h.items.size() / 3);
-  st.items = h.items.data();
-  st.lit = (const uint8_t*)h.lit.data();
-  st.lit_len = (uint32_t)h.lit.size();
-  st.cp_len = (uint32_t)h.cp_u8.size();
-  memcpy(st.cp_u8, h.cp_u8.data(), h.cp_u8.size());
-  return st;
+// (the blob must outlive the Step)
+static Step dev_step(const HostStep& h, const StepBlob& blob) {
+  return step_view(h, blob, (const uint8_t*)blob.bytes.data(), 0xFFFFFFFFu);
 }
 
 static void split_step(const Tables& T, const HostStep& h, Batch& b) {
-  Step st = dev_step(h);
+  const StepBlob blob = step_blob(h);
+  Step st = dev_step(h, blob);
   const Ctx x = b.ctx();
   const uint64_t n = b.n, nw = b.words64();
   std::vector<uint8_t> cand(n + 1, 0), mark(n + 1, 0), whit;
@@ -65,6 +56,21 @@ static void split_step(const Tables& T, const HostStep& h, Batch& b) {
     for (uint64_t p = 0; p < n; p++) cand[p] = lit_cand(st, x, p);
     st.cand = cand.data();
     for (uint64_t p = 0; p < n; p++) lit_chain(st, n, p, mark.data());
+    st.mark = mark.data();
+  }
+  std::vector<uint32_t> len;
+  if (h.kind == K_SPLIT && h.mode == M_DFA) {
+    // every start's match, then the chain heads by the running maximum of the matches' ends
+    len.assign(n + 1, 0);
+    for (uint64_t p = 0; p < n; p++) {
+      bool over;
+      len[p] = dfa_len(T, st.dfa, st.dfa.trans, x, p, &over);
+    }
+    uint64_t reach = 0;
+    for (uint64_t p = 0; p < n; p++) {
+      if (len[p] && reach <= p) dfa_walk(len.data(), n, p, mark.data());
+      if (len[p]) reach = std::max<uint64_t>(reach, p + len[p]);
+    }
     st.mark = mark.data();
   }
   if (h.kind == K_SPLIT && h.mode != M_IDENTITY && (h.flags & 15u) == B_REMOVED) {
@@ -100,7 +106,8 @@ static void split_step(const Tables& T, const HostStep& h, Batch& b) {
 
 // false: the count and the write disagree
 static bool rewrite_step(const Tables& T, const HostStep& h, Batch& b) {
-  const Step st = dev_step(h);
+  const StepBlob blob = step_blob(h);
+  const Step st = dev_step(h, blob);
   const Ctx x = b.ctx();
   const uint64_t n = b.n, nw = b.words64();
   std::vector<uint64_t> pos(nw + 1, 0);
@@ -172,7 +179,8 @@ static bool run(const Tables& T, const std::vector<HostStep>& prog, const std::v
       continue;
     }
     // (a text's new offset: the output bytes of the input bytes before it)
-    const Step st = dev_step(h);
+    const StepBlob blob = step_blob(h);
+    const Step st = dev_step(h, blob);
     const Ctx x = b.ctx();
     std::vector<uint64_t> before(b.n + 1, 0);
     uint8_t unit[kMaxUnit];
@@ -244,7 +252,7 @@ int main(int argc, char** argv) {
     std::string a(len, '\0');
     if (!read_all(&a[0], len)) return 2;
     bool unsupported;
-    if (make_step(kfc[0] & 0xFFu, kfc[1], a, kfc[2], (kfc[0] & 0x100u) != 0, &prog[i], &unsupported)) return unsupported ? 7 : 5;
+    if (!make_step(kfc[0] & 0xFFu, kfc[1], a, kfc[2], (kfc[0] & 0x100u) != 0, &prog[i], &unsupported).empty()) return unsupported ? 7 : 5;
   }
   uint64_t n = 0;
   if (!read_all(&n, 8)) return 2;

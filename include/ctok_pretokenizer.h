@@ -10,7 +10,12 @@
  *
  * A `split` pattern the Rust regex crate rejects is the identity, as in the reference; one it
  * compiles runs when it is a literal or one class atom with an optional '+' (csrc/pretok_prog.h),
- * and is CTOK_E_UNSUPPORTED otherwise.  A batch whose input, or the output of any step, reaches
+ * and is CTOK_E_UNSUPPORTED otherwise, unless the step carries CTOK_PRETOK_REGEX: then a pattern of
+ * literals, '.', those class atoms, concatenation, '|', groups and ? * + {n} {n,} {n,m} (greedy or
+ * lazy) that cannot match the empty string runs as a DFA (csrc/regex_dfa.h), leftmost-first as the
+ * crate matches.  Such a pattern with unbounded matches has a work bound: a word in which a match may
+ * run past ctok_pretok_limits().max_regex_run code points makes the run CTOK_E_UNSUPPORTED, naming the
+ * lowest-numbered such text, with nothing written.  A batch whose input, or the output of any step, reaches
  * 4 GiB is CTOK_E_CAPACITY, decided after the count and before any write.
  *
  * Errors: 0 or a negative CTOK_E_* code (ctok.h), ctok_last_error() holds the message.  There is no
@@ -42,7 +47,7 @@ enum {
   CTOK_PRETOK_BERT = 7,
   CTOK_PRETOK_CHAR_DELIMITER = 8,  /* cp: the delimiter */
   CTOK_PRETOK_UNICODE_SCRIPTS = 9,
-  CTOK_PRETOK_SPLIT = 10           /* a: the pattern; flags & 7: CTOK_PRETOK_*; flags & 8: invert */
+  CTOK_PRETOK_SPLIT = 10           /* a: the pattern; flags & 7: CTOK_PRETOK_*; flags & 8: invert; flags & 16: regex */
 };
 
 /* SplitBehavior */
@@ -52,6 +57,9 @@ enum {
 #define CTOK_PRETOK_MERGED_WITH_NEXT 3u
 #define CTOK_PRETOK_CONTIGUOUS 4u
 #define CTOK_PRETOK_INVERT 8u
+/* On CTOK_PRETOK_SPLIT: a pattern that is neither a literal nor a class atom may run as a DFA.  A
+ * literal or class atom keeps its path, and without the flag nothing changes. */
+#define CTOK_PRETOK_REGEX 16u
 
 #define CTOK_PRETOK_MAX_STEPS 1024
 
@@ -70,6 +78,34 @@ void ctok_pretokenizer_destroy(ctok_pretokenizer* pt);
 /* How a `split` pattern runs: 0 the Rust crate rejects it (the step is the identity), 1 a literal,
  * 2 a class atom, 3 unsupported.  Needs no device. */
 int ctok_pretok_split_class(const uint8_t* pattern, uint64_t len);
+
+/* How a `split` pattern runs under CTOK_PRETOK_REGEX: gate 0..3 as ctok_pretok_split_class says (3:
+ * still refused, `reason` names the construct), 4 a DFA, with its sizes.  Needs no device. */
+typedef struct ctok_pretok_split_info {
+  int32_t gate;
+  uint32_t n_symbols;     /* code-point classes of the DFA's alphabet */
+  uint32_t n_states;      /* DFA states, the dead state not counted */
+  uint32_t n_nfa;         /* NFA states after counted repetitions are expanded */
+  uint32_t cyclic;        /* 1: a match can be unbounded, and max_regex_run applies */
+  uint32_t table_in_lds;  /* 1: the kernels keep the transition table in LDS */
+  uint64_t longest_match; /* code points, when not cyclic */
+  uint64_t table_bytes;
+  char reason[256];       /* gates 0 and 3: why; "" otherwise */
+} ctok_pretok_split_info;
+int ctok_pretok_split_plan(const uint8_t* pattern, uint64_t len, ctok_pretok_split_info* out);
+
+/* The bounds of the DFA path.  max_regex_run: the code points one start of a cyclic DFA may step
+ * through; CTOK_PRETOK_MAX_REGEX_RUN, read when a handle is created and by this call, lowers it. */
+typedef struct ctok_pretok_limits_info {
+  uint64_t max_regex_run;
+  uint64_t max_symbols;
+  uint64_t max_states;
+  uint64_t max_nfa_states;
+  uint64_t lds_table_bytes;  /* a transition table of at most this many bytes is kept in LDS */
+  uint64_t scan_tile_bytes;  /* the bytes one wavefront covers in the prefix max of the matches' ends ... */
+  uint64_t scan_round_bytes; /* ... and one round of the carry over the tiles */
+} ctok_pretok_limits_info;
+int ctok_pretok_limits(ctok_pretok_limits_info* out);
 
 /* n_texts host texts through the program.  words has room for words_cap bytes, word_off for
  * word_cap + 1 offsets, text_word for n_texts + 1.  *n_bytes_out and *n_words_out receive the sizes
